@@ -2,6 +2,7 @@
 """Benchmark: FAS V-cycles of the 3D Poisson problem.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mode weak|strong|weak256]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N ... bench.py --gpus N ...      (one rank per GPU)
 
 With --gpus N > 1 and no torchrun environment (WORLD_SIZE unset) the script
@@ -20,6 +21,18 @@ Modes (the domain for N ranks):
            N = 1 is BASELINE's C3 workload on one GPU
   strong   512^3 in total over the N GPUs (C3 exactly, "512^3, 8xMI355X")
   weak256  SURVEY §8(d)'s weak curve: 256^3 per GPU, 512^3 at N = 8
+A plain run sets up, warms up, times the K steps and prints the line: value,
+ms_per_step, the workload and the set-up times.  --dump-outputs DIR then also
+writes what the last timed step left in phi on the finest level (the array a
+caller of mg_fas_vcycle reads back with get_level) as float64 .npy files:
+phi_box_sums.npy, the sum over the 16^3 cells of every box this rank owns in
+my_ids order, and phi_sample.npy, the boxes (ghost layers included) of a
+fixed, seeded sample of 512 boxes over all ranks, with their positions in
+my_ids in phi_sample_boxes.npy; with N > 1 every rank writes its own files,
+<name>_rank<r>.npy.  The inputs are synthetic and the same from run to run.
+
+Everything below is measured or checked only with --full (the --no-* options
+then leave parts of it out), after the timed steps, the parity check before.
 With N > 1 in weak mode the line also carries "c3_strong": the 512^3 problem
 split over the same N GPUs, timed the same way.  Every line carries
 "c4_refined": the one-level-refined octree of BASELINE's C4 (test_refinement,
@@ -378,10 +391,31 @@ def roofline(smoother, per_gpu_cells, boxes_hi, hi):
     return out
 
 
-def run_c3(omg, domain, dist, rank, world, dev, steps, warmup, profile=True):
+DUMP_SEED = 20240607
+DUMP_SAMPLE_BOXES = 512   # over all ranks: 512 x 18^3 doubles = 24 MB
+
+
+def dump_outputs(omg, mg, dirname, rank, world):
+    """phi on the finest level as the last timed step left it (module
+    docstring, --dump-outputs)."""
+    os.makedirs(dirname, exist_ok=True)
+    hi = mg.highest_lvl
+    phi = mg.get_level(hi, omg.tree.MG_IPHI)
+    n = phi.shape[0]
+    pick = np.sort(np.random.default_rng(DUMP_SEED + rank).choice(n, min(n, max(1, DUMP_SAMPLE_BOXES // world)),
+                                                                  replace=False))
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, arr in (("phi_box_sums", phi[:, 1:-1, 1:-1, 1:-1].sum(axis=(1, 2, 3))),
+                      ("phi_sample", phi[pick]), ("phi_sample_boxes", pick.astype(np.float64))):
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
+def run_c3(omg, domain, dist, rank, world, dev, steps, warmup, profile=True, dump=None):
     mg, t_tree, t_alloc = build(omg, domain, dev)
     timer = Timer(dist, mg.ctx)
     dt = timer.time(lambda: omg.mg_fas_vcycle(mg), steps, warmup)
+    if dump:
+        dump_outputs(omg, mg, dump, rank, world)
     cells = float(np.prod(domain))
     out = {"value": cells * steps / dt, "ms_per_step": dt * 1e3 / steps, "domain": [int(d) for d in domain],
            "levels": [mg.lowest_lvl, mg.highest_lvl], "setup_s": {"tree": t_tree, "alloc_and_rhs": t_alloc},
@@ -600,6 +634,11 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--mode", choices=("weak", "strong", "weak256"), default="weak")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write phi of the last step as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity check, the profiled cycle (roofline, per-kernel times), the c3_strong / "
+                         "c4_refined / gs_lex sub-benchmarks and the CPU baseline; the --no-* options leave parts out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile-pass", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the c3_strong / c4_refined sub-benchmarks")
@@ -607,6 +646,10 @@ def main():
     ap.add_argument("--plan-only", action="store_true",
                     help="CPU only: launch the ranks, build each rank's communication plan, check they pair up")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    do_parity, do_profile = a.full and not a.no_parity, a.full and not a.no_profile_pass
+    do_extra, do_cpu = a.full and not a.no_extra, a.full and not a.no_cpu_baseline
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch(a.gpus))
@@ -629,7 +672,7 @@ def main():
         # transport, octree-mg_amd/mg.py _use_host_transport)
         torch.cuda.set_device(local_rank % torch.cuda.device_count())
 
-    parity = None if a.no_parity else c3_parity(dist, world)
+    parity = c3_parity(dist, world) if do_parity else None
     if parity and parity["ok"] is False:
         if rank == 0:
             print(json.dumps({"metric": METRIC, "value": None, "unit": "cell-updates/s", "n_gpus": world,
@@ -640,12 +683,12 @@ def main():
         sys.exit(PARITY_EXIT)
     domain = domain_for(a.mode, world)
     main_run = run_c3(omg, domain, dist, rank, world, local_rank, a.steps, a.warmup,
-                      profile=not a.no_profile_pass)
+                      profile=do_profile, dump=a.dump_outputs)
     extra = {}
-    if not a.no_extra:
+    if do_extra:
         if world > 1 and a.mode != "strong":
             s = run_c3(omg, domain_for("strong", world), dist, rank, world, local_rank, a.steps, a.warmup,
-                       profile=not a.no_profile_pass)
+                       profile=do_profile)
             extra["c3_strong"] = {"workload": "C3: 512^3 in total over the N GPUs (strong scaling)",
                                   "value": s["value"], "ms_per_step": s["ms_per_step"], "domain": s["domain"],
                                   "steps": a.steps, "warmup": a.warmup, "roofline": s.get("roofline"),
@@ -655,7 +698,7 @@ def main():
             extra["gs_lex"] = run_gs(omg, dist, world)
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and do_cpu:
         cpu = cpu_baseline(domain)
 
     if rank == 0:

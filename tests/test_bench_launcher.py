@@ -88,7 +88,7 @@ def test_bench_two_ranks_on_one_gpu():
     share the GPU, so the library takes the host transport over the gloo
     group (RCCL refuses two ranks on one device); the line must report two
     GPUs, the host transport and the weak-scaling workload."""
-    out = _run("--gpus", "2", "--steps", "2", "--warmup", "1", "--mode", "weak256", "--no-cpu-baseline",
+    out = _run("--gpus", "2", "--steps", "2", "--warmup", "1", "--mode", "weak256", "--full", "--no-cpu-baseline",
                "--no-extra")
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["value"] > 0
     assert out["comm"]["transport"] == "host", out["comm"]
@@ -102,9 +102,69 @@ def test_bench_parity_mismatch_exits_nonzero():
     """A history that differs from the reference's (one bit flipped by the
     test hook OMG_BENCH_PARITY_CORRUPT) stops the bench before anything is
     timed: exit 3, a line with parity false and no value."""
-    out = _run("--gpus", "2", "--mode", "weak256", "--no-cpu-baseline", "--no-extra",
+    out = _run("--gpus", "2", "--mode", "weak256", "--full", "--no-cpu-baseline", "--no-extra",
                env_extra={"OMG_BENCH_PARITY_CORRUPT": "1"}, rc=3)
     assert out["parity"]["ok"] is False and out["parity"]["first_mismatch"] == 3 and out["value"] is None
+
+
+class _FakeMG:
+    """get_level as bench.dump_outputs calls it: n boxes of 16^3 + ghosts."""
+    highest_lvl = 3
+
+    def __init__(self, n):
+        import numpy as np
+        self.phi = np.random.default_rng(5).standard_normal((n, 18, 18, 18))
+
+    def get_level(self, lvl, iv):
+        assert lvl == self.highest_lvl
+        return self.phi
+
+
+@pytest.mark.parametrize("n,world,rank", [(700, 1, 0), (700, 4, 3), (40, 1, 0)])
+def test_dump_outputs_writes_a_fixed_sample(tmp_path, n, world, rank):
+    """--dump-outputs: float64 .npy files, every box's sum and a sample of
+    whole boxes that is the same from call to call (seeded), 512 boxes over
+    all ranks at the most; ranks of a multi-rank run write files of their own."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    omg = bench.__graft_entry__.load_package()
+    mg = _FakeMG(n)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    got = []
+    for d in ("a", "b"):
+        bench.dump_outputs(omg, mg, str(tmp_path / d), rank, world)
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == sorted(f"{k}{suffix}.npy" for k in ("phi_box_sums", "phi_sample", "phi_sample_boxes"))
+        got.append({f: np.load(tmp_path / d / f) for f in files})
+        assert all(a.dtype == np.float64 for a in got[-1].values())
+    assert all(np.array_equal(got[0][f], got[1][f]) for f in got[0])
+    sums, sample, boxes = (got[0][f"{k}{suffix}.npy"] for k in ("phi_box_sums", "phi_sample", "phi_sample_boxes"))
+    pick = boxes.astype(int)
+    assert len(pick) == min(n, 512 // world) and len(set(pick)) == len(pick) and (np.diff(pick) > 0).all()
+    assert np.array_equal(sample, mg.phi[pick])
+    assert np.array_equal(sums, mg.phi[:, 1:-1, 1:-1, 1:-1].sum(axis=(1, 2, 3)))
+    assert bench.DUMP_SAMPLE_BOXES * 18 ** 3 * 8 + 8 * 8 * 512 ** 3 // 16 ** 3 < 64 * 2 ** 20   # C3 at 8 ranks
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump(tmp_path):
+    """A plain run times the steps and nothing else: value and ms_per_step
+    agree, no parity / roofline / sub-benchmark / CPU baseline on the line;
+    --dump-outputs leaves phi of the last step, its box sums those of the
+    sampled boxes."""
+    import numpy as np
+    out = _run("--gpus", "1", "--steps", "3", "--warmup", "1", "--mode", "weak256", "--dump-outputs", str(tmp_path))
+    assert out["steps"] == 3 and out["dtype"] == "f64" and out["higher_is_better"] is True
+    assert out["ms_per_step"] > 0 and out["value"] == pytest.approx(256 ** 3 / (out["ms_per_step"] * 1e-3), rel=1e-9)
+    for key in ("parity", "roofline", "cpu_baseline", "kernels_one_cycle"):
+        assert out[key] is None, key
+    assert not {"c4_refined", "gs_lex", "c3_strong"} & set(out)
+    sums, sample, boxes = (np.load(tmp_path / f"{k}.npy") for k in ("phi_box_sums", "phi_sample", "phi_sample_boxes"))
+    assert sums.shape == (16 ** 3,) and sample.shape == (512, 18, 18, 18) and sample.dtype == np.float64
+    assert np.isfinite(sample).all() and np.abs(sample).max() > 0.1   # u = prod(sin): phi has converged towards it
+    # (two sums of n = 16^3 values, |phi| <= ~1, in possibly different orders: each within n 2^-53 sum|phi| < 2e-9)
+    assert np.abs(sample[:, 1:-1, 1:-1, 1:-1].sum(axis=(1, 2, 3)) - sums[boxes.astype(int)]).max() < 4e-9
 
 
 def test_parity_verdict():
