@@ -106,7 +106,12 @@ int omg_tree_setup(omg_ctx *ctx, int n_boxes, const int *lvl, const int *parent,
 /* mg_set_methods equivalents (src/m_multigrid.f90:27-60; the operators'
  * *_set_methods: m_laplacian.f90:13-49, m_vlaplacian.f90:13-49,
  * m_helmholtz.f90:18-37, m_vhelmholtz.f90:19-49, m_ahelmholtz.f90:19-57;
- * lambda as helmholtz_set_lambda m_helmholtz.f90:39-46 and its v/a forms). */
+ * lambda as helmholtz_set_lambda m_helmholtz.f90:39-46 and its v/a forms).
+ * omg_set_smoother may be called between cycles with other values; the next
+ * cycle uses them (the reference reads mg%n_cycle_down, n_cycle_up,
+ * max_coarse_cycles and residual_coarse_* afresh every cycle).  A count of 0
+ * means no smoothing on that leg; a negative count is stored as 0, which is
+ * what the reference's zero-trip loops make of it. */
 int omg_set_operator(omg_ctx *ctx, int op, double lambda);
 int omg_set_smoother(omg_ctx *ctx, int smoother, int n_cycle_down, int n_cycle_up,
                      int max_coarse_cycles, double residual_coarse_abs,

@@ -1828,8 +1828,14 @@ double fas_vcycle(omg_ctx* c, int highest_lvl, bool want_max_res, bool standalon
     Level* L = level_ptr(c, max_lvl);
     bool need = !(L && L->phi_gc_ok && (!L->any_rb || c->n_ranks == 1 || !c->subtract_mean));
     // (ghosts deferred by the last cycle: its first pass reads none, k_gsrb4 /
-    // k_gsrb3, and writes them all; smooth_boxes fills first otherwise)
-    if (L && L->gc_deferred && c->smoother == OMG_SMOOTHER_GSRB && tail_top(c, max_lvl) < max_lvl) need = false;
+    // k_gsrb3, and writes them all; smooth_boxes fills first otherwise).
+    // Only when this cycle smooths on the way down: the counts may have
+    // changed since the deferral was made, and with n_cycle_down = 0 (a
+    // zero-trip loop in the reference, m_multigrid.f90:407) smooth_boxes
+    // launches nothing and update_coarse's residual reads the ghosts next
+    if (L && L->gc_deferred && c->smoother == OMG_SMOOTHER_GSRB && tail_top(c, max_lvl) < max_lvl &&
+        c->n_cycle_down * c->n_substeps >= 1)
+      need = false;
     if (c->n_ranks > 1 && c->check_collective && (allreduce(c, need ? 1.0 : 0.0, true) > 0.5) != need)
       throw OmgError("mg_fas_vcycle: the stand-alone fill decision differs across ranks "
                      "(an upload of phi was not made on every rank)");
@@ -1858,6 +1864,9 @@ double fas_vcycle(omg_ctx* c, int highest_lvl, bool want_max_res, bool standalon
     // C3's down pass 837 -> 713 us and the residual 590 -> 750 us, the x faces'
     // cells 64 B apart in the neighbours' boxes; profiles/r06/s19_defer_down_ab.txt)
     smooth_boxes(c, l, c->n_cycle_down, 1, fused ? 1 : 0, false, four, four);
+    // (update_coarse reads the level's ghosts: no smoothing above consumed a
+    // deferral, e.g. a cycle that is not stand-alone with n_cycle_down = 0)
+    if (Level* Fd = level_ptr(c, l); Fd && Fd->gc_deferred) fill_gc_lvl(c, l, 1);
     update_coarse(c, l, fused, tail_crhs && l == top + 1);
     faces_join(c, level_ptr(c, l));   // (update_coarse joined them; defensive)
   }
@@ -3639,8 +3648,9 @@ int omg_set_smoother(omg_ctx* c, int smoother, int n_cycle_down, int n_cycle_up,
     c->smoother = smoother;
     c->n_substeps = smoother == OMG_SMOOTHER_GSRB ? 2 : 1;
     ensure_rhs_lex(c);
-    c->n_cycle_down = n_cycle_down;
-    c->n_cycle_up = n_cycle_up;
+    // (negative counts: the reference's loops run zero times, m_multigrid.f90:407)
+    c->n_cycle_down = std::max(n_cycle_down, 0);
+    c->n_cycle_up = std::max(n_cycle_up, 0);
     c->max_coarse_cycles = max_coarse_cycles;
     c->res_abs = res_abs;
     c->res_rel = res_rel;

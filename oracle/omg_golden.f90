@@ -20,7 +20,14 @@
 !              1/2 per iteration, dt = the lambda argument; op helm ->
 !              diffusion_solve with D = 0.5, vhelm -> diffusion_solve_vcoeff,
 !              ahelm -> diffusion_solve_acoeff; max_res 1e-8)
-!     smoother gs | gsrb
+!     smoother gs | gsrb, with an optional suffix of solver parameters
+!              gs|gsrb[:down:up[:max_coarse[:res_abs[:res_rel]]]]:
+!              mg%n_cycle_down, mg%n_cycle_up, mg%max_coarse_cycles,
+!              mg%residual_coarse_abs, mg%residual_coarse_rel (the reference
+!              reads them afresh every cycle, m_multigrid.f90:187,203-207,223);
+!              fields left out keep their defaults (m_data_structures.f90:
+!              318-327).  Tolerances other than the default are given as powers
+!              of two, which every reader converts to the same double
 !     op       lpl | helm | vlpl | vhelm   (v*: coefficient eps in var 5, solution in 6)
 !              | ahelm (eps1..3 in vars 5..7, solution in 8; the dump holds rhs)
 !     bc       sol (callback Dirichlet u) | d0 (Dirichlet 0) | per (periodic)
@@ -64,6 +71,8 @@ program omg_golden
   integer             :: n, ierr, maxres_flag, i_sol, order, n_tree, n_trees
   real(dp)            :: shift(NDIM) = 0.0_dp
   real(dp)            :: max_res, t0, t1
+  integer             :: n_params
+  real(dp)            :: params(5)
   real(dp), parameter :: diff_coeff = 0.5_dp, diff_tol = 1.0e-8_dp
   type(mg_t)          :: mg
 
@@ -75,6 +84,7 @@ program omg_golden
   call get_command_argument(5, arg); read(arg, *) n_its
   call get_command_argument(6, a_cycle)
   call get_command_argument(7, a_smoother)
+  call split_params(a_smoother, params, n_params)
   call get_command_argument(8, a_op)
   call get_command_argument(9, arg); read(arg, *) lambda
   call get_command_argument(10, a_bc)
@@ -151,6 +161,15 @@ program omg_golden
   end select
 
   call mg_set_methods(mg)
+  ! the smoother token's suffix (before anything reads the fields: the GPU
+  ! drop-in pushes them with the tree's data)
+  if (n_params >= 2) then
+     mg%n_cycle_down = nint(params(1))
+     mg%n_cycle_up = nint(params(2))
+  end if
+  if (n_params >= 3) mg%max_coarse_cycles = nint(params(3))
+  if (n_params >= 4) mg%residual_coarse_abs = params(4)
+  if (n_params >= 5) mg%residual_coarse_rel = params(5)
   call mg_comm_init(mg)
 
   n = len_trim(a_lb)
@@ -246,6 +265,30 @@ program omg_golden
   call mpi_finalize(ierr)
 
 contains
+
+  !> "name:p1:p2:..." -> name, the numbers after it and their count
+  subroutine split_params(token, vals, n_vals)
+    character(len=*), intent(inout) :: token
+    real(dp), intent(out)           :: vals(:)
+    integer, intent(out)            :: n_vals
+    character(len=len(token))       :: rest
+    integer                         :: i, m
+    n_vals = 0
+    vals = 0.0_dp
+    m = index(token, ":")
+    if (m == 0) return
+    rest = token(m+1:)
+    token = token(1:m-1)
+    n_vals = 1
+    do i = 1, len_trim(rest)
+       if (rest(i:i) == ":") then
+          rest(i:i) = " "
+          n_vals = n_vals + 1
+       end if
+    end do
+    if (n_vals == 1 .or. n_vals > size(vals)) error stop "bad smoother parameters"
+    read(rest, *) vals(1:n_vals)
+  end subroutine split_params
 
   real(dp) function solution(r)
     real(dp), intent(in) :: r(NDIM)

@@ -27,7 +27,7 @@ MPIEXEC = "/opt/conda/bin/mpiexec"
 # BIG: too large for the CPU oracle in the quick CPU suite (the device is
 # compared with the reference's numbers directly; tests/test_gpu_parity.py)
 BIG = {"c3_per512_box16", "c2_256_box16_gsrb_d0", "c2_256_box16_gs_d0", "c5_helm256_box16_gsrb_d0",
-       "per256_box16_helm_v", "per256_box16_gsrb_f", "mx1_256_box16"}
+       "per256_box16_helm_v", "per256_box16_gsrb_f", "mx1_256_box16", "cyc_per256_box16_0_2"}
 CONFIGS = {
     # tests/test_uniform_grid 8 64 64 64 10 f, as shipped (GS)
     "c1_gs_v": ("8 64 64 64 10 v gs lpl 0 sol sol 1 lb 0", False, [1, 4]),
@@ -134,6 +134,70 @@ CONFIGS = {
     # after the FMG without reaching max_res)
     "diff_nonconv_helm_per_ref2": ("8 32 32 32 3 d2 gs helm 0.01 per phi 2 lb 0", False, [1], True),
     "diff_nonconv_vhelm_sol": ("8 32 32 32 3 d2 gs vhelm 0.001 sol phi 1 lb 0", False, [1], True),
+    # Smoothing counts and coarse-solve limits other than the defaults (the
+    # smoother token's suffix :down:up[:max_coarse[:res_abs[:res_rel]]],
+    # omg_golden.f90; the reference reads the fields afresh every cycle,
+    # m_multigrid.f90:187,203-207,223).  A count of 0 is a zero-trip loop there.
+    # box 8, Dirichlet, GSRB (0:0:3: no smoothing but the coarse solve's, capped)
+    "cyc_d0_gsrb_0_1": ("8 32 32 32 3 v gsrb:0:1 lpl 0 d0 sol 1 lb 1", True, [1]),
+    "cyc_d0_gsrb_1_0": ("8 32 32 32 3 v gsrb:1:0 lpl 0 d0 sol 1 lb 1", True, [1]),
+    "cyc_d0_gsrb_3_1": ("8 32 32 32 3 v gsrb:3:1 lpl 0 d0 sol 1 lb 1", True, [1]),
+    "cyc_d0_gsrb_0_0_cap3": ("8 32 32 32 3 v gsrb:0:0:3 lpl 0 d0 sol 1 lb 1", True, [1]),
+    # box 8, periodic (the mean shift between cycles)
+    "cyc_per_gsrb_1_1": ("8 32 32 32 4 v gsrb:1:1 lpl 0 per sol 1 lb 0", True, [1]),
+    "cyc_per_gsrb_0_2": ("8 32 32 32 4 v gsrb:0:2 lpl 0 per sol 1 lb 0", True, [1, 4]),
+    "cyc_per_gsrb_3_2": ("8 32 32 32 4 v gsrb:3:2 lpl 0 per sol 1 lb 0", True, [1]),
+    # lexicographic GS (odd and even sweep counts per level), and its
+    # register ring at box 16
+    "cyc_d0_gs_1_2": ("8 32 32 32 3 v gs:1:2 lpl 0 d0 sol 1 lb 1", True, [1]),
+    "cyc_d0_gs_0_1": ("8 32 32 32 3 v gs:0:1 lpl 0 d0 sol 1 lb 1", True, [1]),
+    "cyc_d0_gs_3_3": ("8 32 32 32 3 v gs:3:3 lpl 0 d0 sol 1 lb 1", True, [1]),
+    "cyc_d0_gs_box16_1_2": ("16 64 64 64 3 v gs:1:2 lpl 0 d0 sol 1 lb 1", True, [1]),
+    # FMG
+    "cyc_fmg_gsrb_1_2": ("8 32 32 32 3 f gsrb:1:2 lpl 0 sol sol 1 lb 1", True, [1]),
+    "cyc_fmg_gs_helm_n0_0_2": ("8 32 32 32 3 f gs:0:2 helm 10 n0 sol 1 lb 1", True, [1]),
+    # refined trees (box 8, three levels; box 16, the bench's c4 tree)
+    "cyc_ref3_gsrb_1_3": ("8 32 32 32 4 v gsrb:1:3 lpl 0 d0 sol 3 lb 0", True, [1]),
+    "cyc_ref3_gsrb_0_2": ("8 32 32 32 4 v gsrb:0:2 lpl 0 d0 sol 3 lb 0", True, [1, 3]),
+    "cyc_c4_box16_gsrb_1_1": ("16 128 128 128 3 v gsrb:1:1 lpl 0 sol sol 2 lb 0", True, [1]),
+    "cyc_c4_box16_gsrb_0_2": ("16 128 128 128 3 v gsrb:0:2 lpl 0 sol sol 2 lb 0", True, [1]),
+    # Helmholtz and variable-coefficient Helmholtz
+    "cyc_helm_n0_1_2": ("8 32 32 32 3 v gsrb:1:2 helm 10 n0 sol 1 lb 1", True, [1]),
+    "cyc_helm_n0_0_1": ("8 32 32 32 3 v gsrb:0:1 helm 10 n0 sol 1 lb 1", True, [1]),
+    "cyc_vhelm_sol_1_2": ("8 32 32 32 3 v gsrb:1:2 vhelm 10 sol sol 1 lb 1", True, [1]),
+    "cyc_vhelm_sol_0_1": ("8 32 32 32 3 v gsrb:0:1 vhelm 10 sol sol 1 lb 1", True, [1]),
+    # box 16, periodic 128^3 without the max residual: the finest level takes
+    # the block passes (k_gsrb3 / k_gsrb4) once their level bound is lowered,
+    # and a cycle that ends in k_gsrb4's correction form defers its ghosts
+    # (tests/test_gpu_cycle_counts.py)
+    "cyc_per128_box16_0_2": ("16 128 128 128 4 v gsrb:0:2 lpl 0 per sol 1 lb 0", True, [1, 2]),
+    "cyc_per128_box16_4_2": ("16 128 128 128 4 v gsrb:4:2 lpl 0 per sol 1 lb 0", True, [1]),
+    "cyc_per128_box16_2_4": ("16 128 128 128 4 v gsrb:2:4 lpl 0 per sol 1 lb 0", True, [1]),
+    "cyc_per128_box16_1_1": ("16 128 128 128 4 v gsrb:1:1 lpl 0 per sol 1 lb 0", True, [1]),
+    "cyc_per128_box16_2_3": ("16 128 128 128 4 v gsrb:2:3 lpl 0 per sol 1 lb 0", True, [1]),
+    # the same with physical faces
+    "cyc_mx1_128_box16_0_2": ("16 128 128 128 3 v gsrb:0:2 lpl 0 mx1 sol 1 lb 0", True, [1]),
+    "cyc_mx1_128_box16_4_1": ("16 128 128 128 3 v gsrb:4:1 lpl 0 mx1 sol 1 lb 0", True, [1]),
+    "cyc_mx1_96x128x64_0_2": ("16 96 128 64 3 v gsrb:0:2 lpl 0 mx1 sol 1 lb 0", True, [1]),
+    "cyc_mx1_96x128x64_4_1": ("16 96 128 64 3 v gsrb:4:1 lpl 0 mx1 sol 1 lb 0", True, [1]),
+    # the block passes at their default level bound
+    "cyc_per256_box16_0_2": ("16 256 256 256 3 v gsrb:0:2 lpl 0 per sol 1 lb 0", True, [1]),
+    # the coarse solve's three exits (m_multigrid.f90:203-208): the count cap,
+    # the relative and the absolute test, next to the default run of the same
+    # problem (tests/test_oracle_golden.py checks that each of them binds);
+    # vlpl: an operator whose coarse solve runs level by level on the host
+    "cyc_coarse_default": ("8 32 32 32 3 v gsrb lpl 0 d0 sol 1 lb 1", True, [1]),
+    "cyc_coarse_cap1": ("8 32 32 32 3 v gsrb:2:2:1 lpl 0 d0 sol 1 lb 1", True, [1]),
+    "cyc_coarse_cap3": ("8 32 32 32 3 v gsrb:2:2:3 lpl 0 d0 sol 1 lb 1", True, [1]),
+    "cyc_coarse_rel": ("8 32 32 32 3 v gsrb:2:2:1000:1e-8:0.5 lpl 0 d0 sol 1 lb 1", True, [1]),
+    # (2^-16: with 1.0 the absolute test ends every coarse solve after its
+    # first iteration, as the relative test at 0.5 and the cap of 1 do; at
+    # 2^-16 the three runs differ)
+    "cyc_coarse_abs": ("8 32 32 32 3 v gsrb:2:2:1000:1.52587890625e-05:1e-8 lpl 0 d0 sol 1 lb 1", True, [1]),
+    "cyc_coarse_gs_default": ("8 32 32 32 3 v gs lpl 0 d0 sol 1 lb 1", True, [1]),
+    "cyc_coarse_gs_rel": ("8 32 32 32 3 v gs:2:2:1000:1e-8:0.5 lpl 0 d0 sol 1 lb 1", True, [1]),
+    "cyc_coarse_vlpl_gs_default": ("8 32 32 32 3 v gs vlpl 0 d0 sol 1 lb 1", True, [1]),
+    "cyc_coarse_vlpl_gs_cap2": ("8 32 32 32 3 v gs:2:2:2 vlpl 0 d0 sol 1 lb 1", True, [1]),
 }
 
 

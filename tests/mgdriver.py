@@ -35,11 +35,28 @@ def hexbits(x: float) -> str:
     return "%016X" % struct.unpack("<Q", struct.pack("<d", float(x)))[0]
 
 
+# the reference's defaults (m_data_structures.f90:318-327): n_cycle_down,
+# n_cycle_up, max_coarse_cycles, residual_coarse_abs, residual_coarse_rel
+SOLVER_DEFAULTS = (2, 2, 1000, 1e-8, 1e-8)
+
+
 def parse(args: str) -> dict:
+    """omg_golden's arguments.  The smoother token may carry solver parameters,
+    gs|gsrb[:down:up[:max_coarse[:res_abs[:res_rel]]]]: cycles = (down, up)
+    and coarse = (max, abs, rel), fields left out at their defaults; both None
+    without the suffix."""
     f = args.split()
+    smoother, *p = f[6].split(":")
+    cycles = coarse = None
+    if p:
+        if not 2 <= len(p) <= 5:
+            raise ValueError(f"bad smoother parameters: {f[6]}")
+        v = [int(x) for x in p[:3]] + [float(x) for x in p[3:]]
+        v += SOLVER_DEFAULTS[len(v):]
+        cycles, coarse = (v[0], v[1]), (v[2], v[3], v[4])
     return dict(box=int(f[0]), domain=[int(f[1]), int(f[2]), int(f[3])], n_its=int(f[4]),
-                cycle=f[5], smoother=f[6], op=f[7], lam=float(f[8]), bc=f[9], rhs=f[10],
-                n_levels=int(f[11]), lb=f[12], maxres=int(f[13]))
+                cycle=f[5], smoother=smoother, op=f[7], lam=float(f[8]), bc=f[9], rhs=f[10],
+                n_levels=int(f[11]), lb=f[12], maxres=int(f[13]), cycles=cycles, coarse=coarse)
 
 
 def regrids(cfg: dict) -> bool:
@@ -150,7 +167,10 @@ class OracleBackend:
         # mg_build_rectangle sets subtract_mean for a fully periodic domain
         # (m_build_tree.f90:36-38) whatever the operator's set_methods cleared
         sub = cfg["bc"] == "per"
-        self.o.configure(op=op, lam=cfg["lam"], smoother=sm, subtract_mean=sub)
+        down, up = cfg.get("cycles") or SOLVER_DEFAULTS[:2]
+        cmax, cabs, crel = cfg.get("coarse") or SOLVER_DEFAULTS[2:]
+        self.o.configure(op=op, lam=cfg["lam"], smoother=sm, n_cycle_down=down, n_cycle_up=up,
+                         max_coarse_cycles=cmax, res_abs=cabs, res_rel=crel, subtract_mean=sub)
         _apply_bc(cfg, self.tree, lambda iv, nb, t, v: self.o.set_bc(iv, nb, t, v),
                   lambda iv, a, b, c: self.o.set_bc_faces(iv, a, b, c))
 
@@ -207,6 +227,10 @@ class DeviceBackend:
         mg.operator_type = OPS[cfg["op"]]
         mg.helmholtz_lambda = cfg["lam"]
         mg.smoother_type = T.MG_SMOOTHER_GSRB if cfg["smoother"] == "gsrb" else T.MG_SMOOTHER_GS
+        if cfg.get("cycles"):
+            mg.n_cycle_down, mg.n_cycle_up = cfg["cycles"]
+        if cfg.get("coarse"):
+            mg.max_coarse_cycles, mg.residual_coarse_abs, mg.residual_coarse_rel = cfg["coarse"]
         omg.mg_set_methods(mg)
         omg.mg_comm_init(mg, comm)
         self.mg = mg

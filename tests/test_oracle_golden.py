@@ -22,6 +22,35 @@ GOLDEN = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "golde
 CASES = [(n, r) for n, e in GOLDEN.items() if not e.get("big") and not e.get("custom_rb") for r in e["runs"]]
 
 
+def test_golden_histories_are_finite():
+    """Every recorded scalar is a finite double (a reference run that diverged
+    would pin nothing)."""
+    import math
+    import struct
+    for name, e in GOLDEN.items():
+        for r, run in e["runs"].items():
+            for h in run["history"]:
+                for k in ("err", "res", "max_res"):
+                    v = struct.unpack("<d", struct.pack("<Q", int(h[k], 16)))[0]
+                    assert math.isfinite(v), (name, r, h["it"], k, h[k])
+
+
+# The coarse solve's limits (max_coarse_cycles, residual_coarse_rel / _abs)
+# pin something only where they end the coarse loop earlier than the defaults
+# do: the reference's runs of one problem under each limit must differ.
+@pytest.mark.parametrize("names", [("cyc_coarse_cap1", "cyc_coarse_cap3", "cyc_coarse_default"),
+                                   ("cyc_coarse_rel", "cyc_coarse_abs", "cyc_coarse_default"),
+                                   ("cyc_coarse_gs_rel", "cyc_coarse_gs_default"),
+                                   ("cyc_coarse_vlpl_gs_cap2", "cyc_coarse_vlpl_gs_default")])
+def test_coarse_limits_bind_in_the_reference(names):
+    from tests.mgdriver import parse
+    problems = {tuple(GOLDEN[n]["args"].split()[:6] + GOLDEN[n]["args"].split()[7:]) for n in names}
+    smoothers = {parse(GOLDEN[n]["args"])["smoother"] for n in names}
+    assert len(problems) == 1 and len(smoothers) == 1   # the same problem, only the limits differ
+    digests = [GOLDEN[n]["runs"]["1"]["phi_sha256"] for n in names]
+    assert len(set(digests)) == len(names), dict(zip(names, digests))
+
+
 @pytest.mark.parametrize("name,ranks", CASES, ids=[f"{n}-r{r}" for n, r in CASES])
 def test_oracle_matches_reference(name, ranks):
     e = GOLDEN[name]
