@@ -12,10 +12,17 @@
 ! the highest level, and max_res, as IEEE bit patterns (the test's print_error,
 ! :167-195, which reduces over mpi_comm_world the same way).
 !
-! Usage: omg_free_golden box nx ny nz n_its fft_frac cycle dump
-!   cycle f (FMG, as the test) | v (V-cycle)
-!   dump  x, or a file: final phi interior of every box (ids order per level,
-!         lowest..highest, i fastest), raw float64, 1 rank only
+! Usage: omg_free_golden box nx ny nz n_its fft_frac cycle dump [layout]
+!   cycle  f (FMG, as the test) | v (V-cycle)
+!   dump   x, or a file: final phi interior of every box (ids order per level,
+!          lowest..highest, i fastest), raw float64, 1 rank only
+!   layout c (default): the test's problem, one charge at the centre, r_min 0
+!          a: three off-centre charges of both signs (no flip or permutation
+!             of the axes maps the problem onto itself), r_min 0
+!          b: layout a with the domain's origin at (-0.25, 0.5, 1.0), every
+!             charge shifted with it
+!          rhs and solution are the sums over the charges, accumulated from 0
+!          in the order listed, so that layout c keeps its bit patterns
 #include "cpp_macros.h"
 program omg_free_golden
   use mpi
@@ -24,14 +31,17 @@ program omg_free_golden
   implicit none
 
   integer, parameter  :: i8k = selected_int_kind(18)
-  real(dp), parameter :: gauss_ampl  = 1.0d0
-  real(dp), parameter :: gauss_r0(3) = [0.5d0, 0.5d0, 0.5d0]
-  real(dp), parameter :: gauss_sigma = 0.1d0
+  integer, parameter  :: max_charges = 3
+  integer             :: n_charges = 1
+  real(dp)            :: gauss_ampl(max_charges)  = [1.0d0, 0.0d0, 0.0d0]
+  real(dp)            :: gauss_sigma(max_charges) = [0.1d0, 0.1d0, 0.1d0]
+  real(dp)            :: gauss_r0(3, max_charges) = reshape( &
+       [0.5d0, 0.5d0, 0.5d0, 0.5d0, 0.5d0, 0.5d0, 0.5d0, 0.5d0, 0.5d0], [3, max_charges])
   real(dp), parameter :: pi          = acos(-1.0_dp)
   integer             :: box_size, domain_size(NDIM), n_its, n, ierr, i_sol
   real(dp)            :: dr(NDIM), r_min(NDIM) = 0.0_dp, fft_frac, max_res, t0, t1
   logical             :: periodic(NDIM) = .false.
-  character(len=64)   :: arg, a_cycle, a_dump
+  character(len=64)   :: arg, a_cycle, a_dump, a_layout
   type(mg_t)          :: mg
 
   if (command_argument_count() < 8) error stop "omg_free_golden: need 8 args"
@@ -45,6 +55,25 @@ program omg_free_golden
   a_dump = ""
   call get_command_argument(8, arg)
   if (trim(arg) /= "x") a_dump = arg
+  a_layout = "c"
+  if (command_argument_count() >= 9) call get_command_argument(9, a_layout)
+  select case (trim(a_layout))
+  case ("c")
+  case ("a", "b")
+     n_charges   = 3
+     gauss_ampl  = [0.6d0, -0.35d0, 0.25d0]
+     gauss_sigma = [0.08d0, 0.10d0, 0.07d0]
+     gauss_r0    = reshape([0.30d0, 0.55d0, 0.62d0, 0.66d0, 0.34d0, 0.45d0, &
+          0.45d0, 0.70d0, 0.30d0], [3, max_charges])
+     if (trim(a_layout) == "b") then
+        r_min = [-0.25d0, 0.5d0, 1.0d0]
+        do n = 1, n_charges
+           gauss_r0(:, n) = gauss_r0(:, n) + r_min
+        end do
+     end if
+  case default
+     error stop "omg_free_golden: layout must be c, a or b"
+  end select
 
   dr = 1.0_dp / domain_size
   mg%n_extra_vars = 1
@@ -74,23 +103,33 @@ program omg_free_golden
 
 contains
 
-  elemental function solution(x, y, z) result(val)
+  function solution(x, y, z) result(val)
     real(dp), intent(in) :: x, y, z
-    real(dp)             :: val, rnorm
+    real(dp)             :: val, term, rnorm
     real(dp), parameter  :: fac = 1/(4 * pi)
-    rnorm = norm2([ x, y, z ] - gauss_r0)
-    if (rnorm < sqrt(epsilon(1.0d0))) then
-       val = 2 * fac * gauss_ampl / (sqrt(pi) * gauss_sigma)
-    else
-       val = fac * gauss_ampl * erf(rnorm / gauss_sigma) / rnorm
-    end if
+    integer              :: m
+    val = 0.0_dp
+    do m = 1, n_charges
+       rnorm = norm2([ x, y, z ] - gauss_r0(:, m))
+       if (rnorm < sqrt(epsilon(1.0d0))) then
+          term = 2 * fac * gauss_ampl(m) / (sqrt(pi) * gauss_sigma(m))
+       else
+          term = fac * gauss_ampl(m) * erf(rnorm / gauss_sigma(m)) / rnorm
+       end if
+       val = val + term
+    end do
   end function solution
 
-  elemental function rhs(x, y, z) result(val)
+  function rhs(x, y, z) result(val)
     real(dp), intent(in) :: x, y, z
-    real(dp)             :: val, r(NDIM)
-    r = ([ x, y, z ] - gauss_r0) / gauss_sigma
-    val = -gauss_ampl / (gauss_sigma**3 * pi * sqrt(pi)) * exp(-sum(r**2))
+    real(dp)             :: val, term, r(NDIM)
+    integer              :: m
+    val = 0.0_dp
+    do m = 1, n_charges
+       r = ([ x, y, z ] - gauss_r0(:, m)) / gauss_sigma(m)
+       term = -gauss_ampl(m) / (gauss_sigma(m)**3 * pi * sqrt(pi)) * exp(-sum(r**2))
+       val = val + term
+    end do
   end function rhs
 
   subroutine set_rhs_and_solution(mg)

@@ -27,8 +27,9 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 REF = os.path.join(ROOT, "oracle", "_ref")
 MPIEXEC = "/opt/conda/bin/mpiexec"
 sys.path.insert(0, os.path.join(ROOT, "octree-mg_amd"))
+sys.path.insert(0, ROOT)
 
-# name: (box nx ny nz n_its fft_frac cycle), ranks, keep phi
+# name: (box nx ny nz n_its fft_frac cycle [layout]), ranks, keep phi
 CONFIGS = {
     # tests/test_free_space as shipped (8 64 64 64, fft_frac 0.15, FMG)
     "free64_box8_f": ("8 64 64 64 5 0.15 f", [1, 2, 4], False),
@@ -45,11 +46,27 @@ CONFIGS = {
     "free16_fftonly": ("8 16 16 16 1 1.0 f", [1], True),
     "free24x16_fftonly": ("8 24 16 16 1 1.0 f", [1], True),
     "free32_fftonly": ("8 32 32 32 1 1.0 f", [1, 2], False),
+    # An optional 8th token selects the charge layout (tests/freedriver.py
+    # LAYOUTS).  The problem above is unchanged by every axis flip and, on a
+    # cube, by every axis permutation, so it cannot see exchanged planes or
+    # axes; layout a (three off-centre charges) and b (a with a shifted
+    # origin, every component different) can.  The smallest shapes that keep
+    # each path: an FFT level of 16^3 in 8 boxes, a non-cubic grid, box 16,
+    # the FFT on the lowest level, the FFT level as the highest.
+    "free16a_fftonly": ("8 16 16 16 1 1.0 f a", [1, 2], True),
+    "free24x16a_fftonly": ("8 24 16 16 1 1.0 f a", [1], True),
+    "free32a_f": ("8 32 32 32 2 0.15 f a", [1], False),
+    "free32b_f": ("8 32 32 32 2 0.15 f b", [1, 2, 4], False),
+    "free32b_v": ("8 32 32 32 2 0.15 v b", [1], False),
+    "free48x32b_f": ("8 48 32 32 2 0.15 f b", [1], False),
+    "free64b_box16_f": ("16 64 64 64 2 0.15 f b", [1, 2, 4], False),
+    "free32b_lowest_f": ("8 32 32 32 2 0.001 f b", [1], False),
 }
 
 
 def run(args, ranks, dump):
-    cmd = [os.path.join(REF, "omg_free_golden")] + args.split() + [dump or "x"]
+    from tests.freedriver import driver_argv
+    cmd = [os.path.join(REF, "omg_free_golden")] + driver_argv(args, dump)
     if ranks > 1:
         cmd = [MPIEXEC, "-n", str(ranks)] + cmd
     out = subprocess.run(cmd, capture_output=True, text=True, check=True).stdout
@@ -85,6 +102,8 @@ def highest_phi(args, raw):
 def main():
     if not os.path.exists(os.path.join(REF, "omg_free_golden")):
         sys.exit("build the reference first: make -C oracle ref")
+    out_json = os.path.join(HERE, "free_golden.json")
+    old = json.load(open(out_json))["configs"] if os.path.exists(out_json) else {}
     golden = {}
     for name, (args, ranks, keep) in CONFIGS.items():
         entry = {"args": args, "runs": {}}
@@ -92,6 +111,9 @@ def main():
             with tempfile.TemporaryDirectory() as td:
                 fn = os.path.join(td, "phi.bin") if keep and r == 1 else None
                 its, t = run(args, r, fn)
+                was = old.get(name, {}).get("runs", {}).get(str(r))
+                if was and old[name]["args"] == args and was["history"] == its:
+                    t = was["ref_seconds_per_call"]   # same numbers: keep the recorded wall time too
                 entry["runs"][str(r)] = {"history": its, "ref_seconds_per_call": t}
                 if fn:
                     phi = highest_phi(args, np.fromfile(fn))
@@ -100,7 +122,7 @@ def main():
                     entry["phi_npy"] = npy
             print(name, r, its[-1], file=sys.stderr)
         golden[name] = entry
-    with open(os.path.join(HERE, "free_golden.json"), "w") as f:
+    with open(out_json, "w") as f:
         json.dump({"generator": "tests/golden/make_free_golden.py",
                    "reference": "FermiQ/octree-mg @ 2025-06-14 m_free_space + poisson_3d_fft, "
                                 "amdflang -O2, MPICH 3.3.2",

@@ -186,7 +186,7 @@ def test_dropin_free_space_golden(name):
     if not os.path.exists(FREE_DRIVER):
         pytest.skip("Fortran drop-in drivers not built")
     cfg = FREE_GOLDEN[name]
-    p = subprocess.run([FREE_DRIVER] + cfg["args"].split() + ["x"], capture_output=True, text=True,
+    p = subprocess.run([FREE_DRIVER] + FD.driver_argv(cfg["args"]), capture_output=True, text=True,
                        timeout=300)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     its = []

@@ -21,7 +21,18 @@ GOLDEN = json.load(open(os.path.join(ROOT, "tests", "golden", "free_golden.json"
 fs = FD.omg.free_space
 
 
-@pytest.mark.parametrize("name", ["free16_fftonly", "free24x16_fftonly"])
+_ORACLE_RUNS = {}
+
+
+def _oracle(name):
+    """run_oracle of a golden entry, computed once per module."""
+    if name not in _ORACLE_RUNS:
+        _ORACLE_RUNS[name] = FD.run_oracle(GOLDEN[name]["args"])
+    return _ORACLE_RUNS[name]
+
+
+@pytest.mark.parametrize("name", ["free16_fftonly", "free24x16_fftonly", "free16a_fftonly",
+                                  "free24x16a_fftonly"])
 def test_green_solve_matches_reference_psolver(name):
     """The direct-convolution restatement against PSolver's own result (the
     FFT level is the highest, so the reference's phi is PSolver's output):
@@ -34,7 +45,7 @@ def test_green_solve_matches_reference_psolver(name):
     dr = [1.0 / d for d in dom]
     tree = FD.build_tree(cfg, FD.T.MGTree())
     lvl = tree.highest_lvl
-    rhs, _ = FD.level_fields(tree, lvl, tree.lvls[lvl].ids)
+    rhs, _ = FD.level_fields(tree, lvl, tree.lvls[lvl].ids, cfg["layout"])
     nc = tree.box_size_lvl[lvl]
     rho = np.zeros(nx)
     for n, id_ in enumerate(tree.lvls[lvl].ids):
@@ -47,14 +58,97 @@ def test_green_solve_matches_reference_psolver(name):
 
 
 @pytest.mark.parametrize("name", ["free16_fftonly", "free32_fftonly", "free64_box8_f", "free64_box8_v",
-                                  "free48x32_f", "free64_lowest_f"])
+                                  "free48x32_f", "free64_lowest_f", "free16a_fftonly", "free24x16a_fftonly",
+                                  "free32a_f", "free32b_f", "free32b_v", "free48x32b_f", "free64b_box16_f",
+                                  "free32b_lowest_f"])
 def test_oracle_free_space_matches_reference_history(name):
     """mg_poisson_free_3d restated over the C oracle: every iteration's max
     error, rms error and max_res as the reference printed them, within the
     stated round-off tolerance."""
     e = GOLDEN[name]
-    out = FD.run_oracle(e["args"])
+    out = _oracle(name)
     FD.compare_history(out["history"], FD.golden_history(e), FD.parse(e["args"]), name)
+
+
+def test_driver_argv_places_the_layout_after_the_dump():
+    assert FD.driver_argv("8 16 16 16 1 1.0 f") == "8 16 16 16 1 1.0 f x".split()
+    assert FD.driver_argv("8 16 16 16 1 1.0 f a") == "8 16 16 16 1 1.0 f x a".split()
+    assert FD.driver_argv("8 16 16 16 1 1.0 f b", "out.bin") == "8 16 16 16 1 1.0 f out.bin b".split()
+    assert FD.parse("8 16 16 16 1 1.0 f")["layout"] == "c"
+    assert FD.parse("8 16 16 16 1 1.0 f b")["layout"] == "b"
+
+
+# -- the asymmetric fixtures discriminate --------------------------------------
+# Indexing errors that the centred Gaussian cannot see (it is unchanged by
+# every axis flip and, on a cube, by every permutation), planted in the
+# oracle: each must miss the reference's golden.  Checked on the reference and
+# the oracle alone, so that the GPU tests against these goldens are not vacuous.
+
+def _swap_low_high(orig):
+    return lambda planes, nb, *a: orig(planes, nb + 1 if nb % 2 else nb - 1, *a)
+
+
+def _transpose_square(orig):
+    def interp(planes, nb, *a):
+        sq = [P.T if P.shape[0] == P.shape[1] else P for P in planes]
+        return orig(sq, nb, *a)
+    return interp
+
+
+def _swap_yz(orig):
+    def solve(rho, h, n0k=None):
+        assert rho.shape[1] == rho.shape[2] and h[1] == h[2]
+        return orig(np.ascontiguousarray(rho.transpose(0, 2, 1)), h, n0k)
+    return solve
+
+
+def _swap_mirror_boxes(nc):
+    def wrap(orig):
+        def solve(rho, h, n0k=None):
+            rho = rho.copy()
+            lo, hi = slice(1, 1 + nc), slice(rho.shape[0] - 1 - nc, rho.shape[0] - 1)
+            b = slice(1, 1 + nc)   # the boxes ix = (1, 1, 1) and (nbx, 1, 1)
+            rho[lo, b, b], rho[hi, b, b] = rho[hi, b, b].copy(), rho[lo, b, b].copy()
+            return orig(rho, h, n0k)
+        return solve
+    return wrap
+
+
+_MUTANTS = {
+    "low_high_planes_swapped": ("_interp", _swap_low_high),
+    "square_planes_transposed": ("_interp", _transpose_square),
+    "density_yz_exchanged": ("free_solve", _swap_yz),
+    "mirror_boxes_exchanged": ("free_solve", _swap_mirror_boxes(8)),
+}
+
+
+@pytest.mark.parametrize("name,mutant", [(n, m) for n in ("free32b_f", "free48x32b_f") for m in _MUTANTS
+                                         if not (m == "density_yz_exchanged" and n != "free32b_f")])
+def test_asymmetric_goldens_reject_indexing_mutants(name, mutant, monkeypatch):
+    e = GOLDEN[name]
+    cfg = FD.parse(e["args"])
+    assert cfg["box"] == 8
+    attr, make = _MUTANTS[mutant]
+    monkeypatch.setattr(F, attr, make(getattr(F, attr)))
+    out = FD.run_oracle(e["args"])
+    monkeypatch.undo()
+    with pytest.raises(AssertionError):
+        FD.compare_history(out["history"], FD.golden_history(e), cfg, name + ":" + mutant)
+    # and the unmutated oracle passes the same comparison
+    FD.compare_history(_oracle(name)["history"], FD.golden_history(e), cfg, name)
+
+
+def test_layout_b_planes_are_asymmetric():
+    """Each low/high pair of the boundary planes differs, and each square
+    plane differs from its transpose, far above any tolerance: exchanged or
+    transposed planes cannot pass a comparison on this layout."""
+    out = _oracle("free32b_f")
+    P = out["planes_2d"]
+    for q in range(3):
+        assert np.max(np.abs(P[2 * q] - P[2 * q + 1])) > 1e-3, q
+    for n, p in enumerate(P):
+        assert p.shape[0] == p.shape[1]
+        assert np.max(np.abs(p - p.T)) > 1e-3, n
 
 
 def test_reference_histories_do_not_depend_on_rank_count():
