@@ -1,5 +1,5 @@
 // omg_free.h — device side of the free-space boundary conditions
-// (m_free_space, kernels in omg_free.hip, driver in omg_api.cpp).
+// (m_free_space, kernels in omg_free.hip, driver in omg_free_host.cpp).
 #pragma once
 
 #include "omg_internal.h"

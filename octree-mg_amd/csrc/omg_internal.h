@@ -197,14 +197,14 @@ struct Level {
   int n_b3 = 0;
   std::vector<int> h_b3;   // (host copy, for the coarse records below)
   // some columns have physical faces (round 6): the passes take the ghosts
-  // there from constant boundary values (b3_phys, omg_api.cpp)
+  // there from constant boundary values (b3_phys, omg_plan.cpp)
   bool b3_phys = false;
   // k_gsrb3's correct_children form: per column the coarse boxes around it
   // (launch_gsrb3's ccols); null: the level's up-smoothing starts with
   // k_prolong_smooth
   int* d_b3c = nullptr;
   // Deep halo (k_gsrb3 / k_gsrb4 on a level split over GPUs, plan_deep in
-  // omg_api.cpp): the remote boxes the columns read are proxy boxes
+  // omg_plan.cpp): the remote boxes the columns read are proxy boxes
   // n .. n+n_prox-1 of every variable (vstride covers them); before a pass the
   // cells the columns read travel as 4^3-cell bricks, phi of the colour the
   // pass reads (deep, 32 doubles per brick) and rhs when it changed since
@@ -288,8 +288,8 @@ struct KStat {
 
 }  // namespace omg
 
-struct omg_loop;          // in-process loopback transport (omg_api.cpp)
-struct omg_free_state;    // free-space boundary conditions (omg_api.cpp, omg_free.hip)
+struct omg_loop;          // in-process loopback transport (omg_host.h)
+struct omg_free_state;    // free-space boundary conditions (omg_host.h, omg_free.hip)
 
 namespace omg {
 struct TailArgs;   // omg_kernels.h

@@ -212,7 +212,7 @@ struct TailArgs {
   long long* stamps;             // OMG_TAIL_TIMING: wall clock per phase (thread 0), or null
   // levels 0..lds_levels-1 run with their box resident in LDS (at most 8^3
   // cells, a single box whose local faces are itself), and lds_top: the 16^3
-  // top level above them too (tail_lds_plan in omg_api.cpp)
+  // top level above them too (tail_lds_plan in omg_cycle.cpp)
   int lds_levels, lds_top;
   // the tail forms the top level's ghosts and its coarse rhs = L(phi) + res,
   // old = phi itself (update_coarse of top+1 stopped after the restriction)

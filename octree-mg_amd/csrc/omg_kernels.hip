@@ -58,7 +58,7 @@ __global__ void __launch_bounds__(256) k_unpack_faces(LevelView L, int iv, const
 }
 
 // Deep halo of a level split over GPUs (k_gsrb3 / k_gsrb4 on split levels,
-// omg_api.cpp plan_deep): a remote box that some column here reads is held
+// omg_plan.cpp plan_deep): a remote box that some column here reads is held
 // as a proxy box after this rank's boxes in every variable, and the cells the
 // columns read (4 layers toward this rank's boxes, whole across) travel as
 // 4 x 4 x 4 bricks, brick = bx + 4 by + 16 bz.  per = 32: one colour c of

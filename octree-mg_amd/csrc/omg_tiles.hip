@@ -1447,7 +1447,7 @@ __device__ void tail_correct(const TailArgs& A, int li, double* lds) {
 // formulas), so the results are bit-identical; only the L2 round trips and
 // the per-step LDS staging go away.  The one-box levels of the tail are
 // single boxes whose local neighbours are the box itself (periodic faces);
-// run_tail (omg_api.cpp) checks that when it sets lds_levels / lds_top.
+// run_tail (omg_cycle.cpp) checks that when it sets lds_levels / lds_top.
 constexpr int kTailLdsLevels = kTailLdsMaxLevels;
 constexpr int kTailLdsDoubles = 4 * (10 * 10 * 10 + 6 * 6 * 6 + 4 * 4 * 4);
 // the physical bc values of each face cell of each level, resolved once

@@ -115,7 +115,7 @@ def fft_level(mg: MG, max_fft_frac: float) -> int:
 
 
 def fft_length(m: int) -> int:
-    """Transform length of one padded axis (omg_api.cpp fft_length): the
+    """Transform length of one padded axis (omg_free_host.cpp fft_length): the
     smallest even n >= m with prime factors 2, 3, 5, 7."""
     n = max(m, 2)
     while True:

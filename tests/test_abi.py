@@ -44,6 +44,33 @@ def test_library_is_gfx950_code_object():
     assert b"gfx950" in data
 
 
+def test_library_exports_only_its_own_names():
+    """Every defined, non-weak dynamic symbol is an entry point of
+    include/omg.h, a name under namespace omg, or the HIP runtime's
+    registration data.  User programs link against this library (the Fortran
+    drop-in), so a plain global such as a helper left inside the extern "C"
+    block would collide with theirs.  (llvm-readelf's GLOBAL binding of a
+    defined FUNC / OBJECT / TLS symbol is what nm prints as T, D or B; the
+    WEAK ones, nm's W / V, are template instantiations.)"""
+    out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--dyn-syms", "-W", LIB],
+                         capture_output=True, text=True, check=True).stdout
+    entry_points = set(declared())
+    seen, foreign = 0, []
+    for line in out.splitlines():
+        f = line.split()
+        # Num: Value Size Type Bind Vis Ndx Name
+        if len(f) != 8 or not f[0].rstrip(":").isdigit() or f[6] == "UND":
+            continue
+        if f[4] != "GLOBAL" or f[3] not in ("FUNC", "OBJECT", "TLS"):
+            continue
+        seen += 1
+        name = f[7].split("@")[0]
+        if not (name in entry_points or name.startswith(("_ZN3omg", "_ZNK3omg", "__hip_"))):
+            foreign.append(name)
+    assert seen >= len(entry_points)   # (the listing was understood)
+    assert not foreign, foreign
+
+
 def test_last_error_without_gpu_is_clean():
     from tests.mgdriver import omg
     L = omg.device.lib()

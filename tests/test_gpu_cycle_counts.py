@@ -3,7 +3,7 @@
 The reference reads mg%n_cycle_down, n_cycle_up, max_coarse_cycles and
 residual_coarse_abs / _rel afresh every cycle (m_multigrid.f90:187,203-207,
 223), so they may change between cycles, and a count of 0 is a zero-trip loop.
-fas_vcycle (octree-mg_amd/csrc/omg_api.cpp) chooses its kernels by the counts:
+fas_vcycle (octree-mg_amd/csrc/omg_cycle.cpp) chooses its kernels by the counts:
 k_gsrb4 down passes where the substeps are a multiple of four, k_smooth_resid
 where there is a last down substep to fuse, k_gsrb3 / k_gsrb4's correction
 forms where the up-smoothing has three / four substeps, an even number of ring

@@ -138,7 +138,7 @@ def test_multirank_vcycle_makes_no_host_wait(args, ranks, monkeypatch):
 
 
 # Round 6: the multi-substep passes on levels split over ranks (the deep halo,
-# omg_api.cpp plan_deep): the remote boxes the columns read are proxies,
+# omg_plan.cpp plan_deep): the remote boxes the columns read are proxies,
 # filled once per pass (phi of the colour read; rhs when it changed, the
 # periodic mean subtracted on them like on their owners), and the remote
 # faces' ghosts exchanged after it.  The 128^3 tree's 512-box finest level

@@ -213,7 +213,7 @@ def test_plans_pair_up_across_ranks(args, world, rep):
         assert sum(n for _, _, n in res) > 0, "case meant to cross refinement boundaries has none"
 
 
-# The deep halo of k_gsrb3 / k_gsrb4 on a split level (omg_api.cpp plan_deep),
+# The deep halo of k_gsrb3 / k_gsrb4 on a split level (omg_plan.cpp plan_deep),
 # with the pass's level bound lowered to one box (OMG_BLOCK3_MIN_BOXES): the
 # brick lists pair up key for key, every rank receives exactly the bricks its
 # columns read (from box coordinates, _expected_deep), and a level whose x

@@ -4,7 +4,7 @@ octree-mg_amd/_variants/libomg_b3p_<name>.so (load with OMG_LIB=...)."""
 import os, shutil, subprocess, sys
 
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILES = {"subnt": "omg_tiles.hip", "subntld": "omg_tiles.hip", "z8": "omg_api.cpp", "z2": "omg_api.cpp"}
+FILES = {"subnt": "omg_tiles.hip", "subntld": "omg_tiles.hip", "z8": "omg_plan.cpp", "z2": "omg_plan.cpp"}
 # (default: omg_block.hip)
 VARIANTS = {
     # the plain pass at 6 waves per SIMD (3 workgroups per CU; 79 VGPRs, 20 B
@@ -73,5 +73,5 @@ for name in names:
         open(p, "w").write(s)
     out = os.path.join(R, "octree-mg_amd", "_variants", f"libomg_b3p_{name}.so")
     subprocess.run(["make", "-j8", "-C", d, f"OUT={out}"], check=True, stdout=subprocess.DEVNULL)
-    # the include path of omg_api.cpp (../../include/omg.h) resolves from the copy's parent
+    # the include path of omg_host.h (../../include/omg.h) resolves from the copy's parent
     print("built", out)
