@@ -138,7 +138,10 @@ int omg_replicated_level(omg_ctx *ctx, int *lvl);
 /* Boundary conditions for variable iv (mg%bc(nb, iv), src/m_data_structures
  * .f90:235-242).  omg_set_bc_faces tabulates a boundary_cond callback:
  * face_off[(id-1)*6 + nb-1] = offset of nc*nc values in data (first
- * tangential index fastest) or -1; face_type = the bc type it returned. */
+ * tangential index fastest) or -1; face_type = the bc type it returned.
+ * Both first fill ghosts that a cycle deferred (under the condition that
+ * held), then mark every level's ghosts stale; with several ranks they are
+ * collective, like every other call that may fill. */
 int omg_set_bc(omg_ctx *ctx, int iv, int nb, int bc_type, double bc_value);
 int omg_set_bc_faces(omg_ctx *ctx, int iv, const long long *face_off,
                      const int *face_type, const double *data, long long n_data);

@@ -335,8 +335,11 @@ int omg_set_subtract_mean(omg_ctx* c, int on) {
 
 int omg_set_bc(omg_ctx* c, int iv, int nb, int bc_type, double bc_value) {
   return guarded([&] {
-    phi_dirty_all(c);
     if (iv < 1 || iv > kMaxVars || nb < 1 || nb > 6) throw OmgError("omg_set_bc: bad iv/nb");
+    // (deferred ghosts are filled under the old condition first, as the
+    // reference's last fill formed them; then every level's ghosts are stale)
+    enter(c, false);
+    phi_dirty_all(c);
     c->bc[iv - 1].type[nb - 1] = bc_type;
     c->bc[iv - 1].value[nb - 1] = bc_value;
   });
@@ -346,6 +349,7 @@ int omg_set_bc_faces(omg_ctx* c, int iv, const long long* face_off, const int* f
                      const double* data, long long n_data) {
   return guarded([&] {
     if (iv < 1 || iv > kMaxVars) throw OmgError("omg_set_bc_faces: bad iv");
+    if (!c->host_only) enter(c, false);   // (as omg_set_bc)
     phi_dirty_all(c);
     const int k = iv - 1;
     for (auto& kv : c->d_face_off_lvl[k]) dfree(kv.second);
@@ -572,7 +576,14 @@ int omg_get_sum(omg_ctx* c, int iv, double* out) {
   });
 }
 int omg_subtract_mean(omg_ctx* c, int iv, int include_ghostcells) {
-  return guarded([&] { subtract_mean(c, iv, include_ghostcells); });
+  return guarded([&] {
+    // deferred ghosts are filled first: an interior-only subtraction leaves
+    // the ghosts of the last fill as they are (m_multigrid.f90:262-273), and a
+    // fill made afterwards would form them from the subtracted interior.  The
+    // cached rhs sums stay: subtract_mean itself follows its writes of rhs
+    enter(c, false);
+    subtract_mean(c, iv, include_ghostcells);
+  });
 }
 
 // mg_phi_bc_store (m_ghost_cells.f90:66-117): the bc values of phi go into

@@ -214,6 +214,9 @@ void subtract_mean(omg_ctx* c, int iv, int ghosts, int mode) {
   mean_device(c, ch);
   for (int l = c->lowest; l <= c->highest; l++) {
     Level* L = level_ptr(c, l);
+    // (phi of every level changes: the refinement-boundary coarse parts the
+    // level above stored, Level::rbgv_ok, are those of the old phi)
+    if (L && iv == 1) L->rbgv_ok = false;
     if (L && L->n) {
       Prof p(c, "subtract", (double)L->n * L->nc * L->nc * L->nc, l);
       launch_subtract(L->view(), iv, red_mean(c, ch), ghosts, c->stream);

@@ -16,7 +16,10 @@
 !
 ! Usage (positional):
 !   omg_golden box nx ny nz n_its cycle smoother op lambda bc rhs n_levels lb maxres dump
-!     cycle    v | f | d1 | d2  (d1/d2: one m_diffusion time step of order
+!     cycle    v | f | a | d1 | d2  (a: per iteration a fixed script of calls a
+!              caller makes between cycles, see the loop; its dump is
+!              followed by rhs in <dump>_rhs and by dump_mid's <dump>_mid;
+!              d1/d2: one m_diffusion time step of order
 !              1/2 per iteration, dt = the lambda argument; op helm ->
 !              diffusion_solve with D = 0.5, vhelm -> diffusion_solve_vcoeff,
 !              ahelm -> diffusion_solve_acoeff; max_res 1e-8)
@@ -68,7 +71,7 @@ program omg_golden
   logical             :: periodic(NDIM) = .false.
   real(dp), parameter :: pi = acos(-1.0_dp)
   character(len=64)   :: a_cycle, a_smoother, a_op, a_bc, a_rhs, a_lb, a_dump, arg
-  integer             :: n, ierr, maxres_flag, i_sol, order, n_tree, n_trees
+  integer             :: n, ierr, maxres_flag, i_sol, order, n_tree, n_trees, hi, i_dump
   real(dp)            :: shift(NDIM) = 0.0_dp
   real(dp)            :: max_res, t0, t1
   integer             :: n_params
@@ -231,6 +234,29 @@ program omg_golden
         else
            call diffusion_solve_acoeff(mg, lambda, order, diff_tol)
         end if
+     else if (trim(a_cycle) == "a") then
+        ! the entry points a caller reaches between cycles, from outside: a
+        ! cycle to the level below the top, a cycle that is not stand-alone,
+        ! a restriction of rhs, a prolongation of phi into old that does not
+        ! add, a fill of res, then a stand-alone cycle with the max residual;
+        ! a history line after each of the three cycles
+#ifdef OMG_GPU_RESIDENT
+        error stop "omg_golden: cycle a runs host routines between cycles (not in resident mode)"
+#endif
+        hi = mg%highest_lvl
+        call mg_fas_vcycle(mg, highest_lvl=hi-1)
+        call print_state(mg, n, 0.0_dp)
+        call mg_fas_vcycle(mg, standalone=.false.)
+        call print_state(mg, n, 0.0_dp)
+        call mg_restrict_lvl(mg, mg_irhs, hi)
+        call mg_prolong(mg, hi-1, mg_iphi, mg_iold, mg%box_prolong, add=.false.)
+        call mg_fill_ghost_cells_lvl(mg, hi, mg_ires)
+        ! what the three calls wrote is overwritten by the cycle after them
+        ! (rhs of the parents) or never read by one (old on the top level, the
+        ! ghosts of res): rhs, old and res of every box, face ghosts
+        ! included, are dumped here, in the last iteration
+        if (n == n_its .and. len_trim(a_dump) > 0) call dump_mid(mg, trim(a_dump) // "_mid")
+        call mg_fas_vcycle(mg, max_res=max_res)
      else if (trim(a_cycle) == "f") then
         if (maxres_flag == 1) then
            call mg_fas_fmg(mg, n > 1, max_res)
@@ -254,10 +280,14 @@ program omg_golden
   end do
 
   if (len_trim(a_dump) > 0) then
+     i_dump = mg_iphi
+     if (mg%operator_type == mg_ahelmholtz) i_dump = mg_irhs
      if (mg%n_cpu == 1) then
-        call dump_phi(mg, trim(a_dump))
+        call dump_phi(mg, trim(a_dump), i_dump)
+        if (trim(a_cycle) == "a") call dump_phi(mg, trim(a_dump) // "_rhs", mg_irhs)
      else
-        call dump_phi_rank(mg, trim(a_dump))
+        call dump_phi_rank(mg, trim(a_dump), i_dump)
+        if (trim(a_cycle) == "a") call dump_phi_rank(mg, trim(a_dump) // "_rhs", mg_irhs)
      end if
   end if
 
@@ -422,29 +452,27 @@ contains
          transfer(gerr, 0_i8k), transfer(gres, 0_i8k), transfer(mres, 0_i8k), gerr, gres, mres
   end subroutine print_state
 
-  subroutine dump_phi(mg, fname)
+  subroutine dump_phi(mg, fname, iv)
     type(mg_t), intent(inout) :: mg
     character(len=*), intent(in) :: fname
+    integer, intent(in) :: iv
     integer :: u, n, id, lvl, nc
     open(newunit=u, file=fname, access="stream", form="unformatted", status="replace")
     do lvl = mg%lowest_lvl, mg%highest_lvl
        nc = mg%box_size_lvl(lvl)
        do n = 1, size(mg%lvls(lvl)%ids)
           id = mg%lvls(lvl)%ids(n)
-          if (mg%operator_type == mg_ahelmholtz) then
-             write(u) mg%boxes(id)%cc(1:nc, 1:nc, 1:nc, mg_irhs)
-          else
-             write(u) mg%boxes(id)%cc(1:nc, 1:nc, 1:nc, mg_iphi)
-          end if
+          write(u) mg%boxes(id)%cc(1:nc, 1:nc, 1:nc, iv)
        end do
     end do
     close(u)
   end subroutine dump_phi
 
   ! multi-rank: this rank's boxes, each tagged with its place in the one-rank order
-  subroutine dump_phi_rank(mg, fname)
+  subroutine dump_phi_rank(mg, fname, iv)
     type(mg_t), intent(inout) :: mg
     character(len=*), intent(in) :: fname
+    integer, intent(in) :: iv
     character(len=16) :: suffix
     integer :: u, n, id, lvl, nc
     write(suffix, '(A,I0)') ".r", mg%my_rank
@@ -455,15 +483,42 @@ contains
           id = mg%lvls(lvl)%ids(n)
           if (mg%boxes(id)%rank /= mg%my_rank) cycle
           write(u) lvl, n, nc
-          if (mg%operator_type == mg_ahelmholtz) then
-             write(u) mg%boxes(id)%cc(1:nc, 1:nc, 1:nc, mg_irhs)
-          else
-             write(u) mg%boxes(id)%cc(1:nc, 1:nc, 1:nc, mg_iphi)
-          end if
+          write(u) mg%boxes(id)%cc(1:nc, 1:nc, 1:nc, iv)
        end do
     end do
     close(u)
   end subroutine dump_phi_rank
+
+  ! cycle a: rhs, old and res of this rank's boxes, each the interior and then
+  ! the six face ghosts (x-, x+, y-, y+, z-, z+; the edge and corner ghosts no
+  ! routine defines are left out); with several ranks <fname>.r<rank>, each
+  ! box tagged with its place in the one-rank order and its number of doubles
+  subroutine dump_mid(mg, fname)
+    type(mg_t), intent(inout) :: mg
+    character(len=*), intent(in) :: fname
+    character(len=16) :: suffix
+    integer :: u, n, id, lvl, nc, k, iv
+    integer, parameter :: ivs(3) = [mg_irhs, mg_iold, mg_ires]
+    suffix = ""
+    if (mg%n_cpu > 1) write(suffix, '(A,I0)') ".r", mg%my_rank
+    open(newunit=u, file=fname // trim(suffix), access="stream", form="unformatted", status="replace")
+    do lvl = mg%lowest_lvl, mg%highest_lvl
+       nc = mg%box_size_lvl(lvl)
+       do n = 1, size(mg%lvls(lvl)%ids)
+          id = mg%lvls(lvl)%ids(n)
+          if (mg%boxes(id)%rank /= mg%my_rank) cycle
+          if (mg%n_cpu > 1) write(u) lvl, n, 3 * (nc**3 + 6 * nc**2)
+          do k = 1, 3
+             iv = ivs(k)
+             write(u) mg%boxes(id)%cc(1:nc, 1:nc, 1:nc, iv)
+             write(u) mg%boxes(id)%cc(0, 1:nc, 1:nc, iv), mg%boxes(id)%cc(nc+1, 1:nc, 1:nc, iv)
+             write(u) mg%boxes(id)%cc(1:nc, 0, 1:nc, iv), mg%boxes(id)%cc(1:nc, nc+1, 1:nc, iv)
+             write(u) mg%boxes(id)%cc(1:nc, 1:nc, 0, iv), mg%boxes(id)%cc(1:nc, 1:nc, nc+1, iv)
+          end do
+       end do
+    end do
+    close(u)
+  end subroutine dump_mid
 
   !> A refinement-boundary method of the mg_subr_rb interface
   !> (m_data_structures.f90:364-378): sides_rb's second-order form

@@ -217,6 +217,24 @@ void orc_set_box(orc_mg *mg, int id, int iv, const double *in) {
     memcpy(mg->cc[id - 1] + n * (iv - 1), in, sizeof(double) * n);
 }
 
+/* max |value| of variable iv over every cell of every box (the unstored edge
+ * and corner ghosts included), NaN if any cell is NaN: the walks' finiteness
+ * check (tests/test_api_walk_host.py) without a copy of every box. */
+double orc_max_abs(const orc_mg *mg, int iv) {
+    double m = 0.0;
+    int nan = 0;
+    for (int id = 1; id <= mg->n_boxes; id++) {
+        long s = box_nc(mg, id) + 2, n = s * s * s;
+        const double *c = mg->cc[id - 1] + n * (iv - 1);
+        for (long q = 0; q < n; q++) {
+            double x = fabs(c[q]);
+            if (x != x) nan = 1;
+            if (x > m) m = x;
+        }
+    }
+    return nan ? NAN : m;
+}
+
 /* ------------------------------------------------------------------------ */
 /* Face access.  A face array gc(a,b) (a fastest) holds, for x faces gc(j,k),
  * for y faces gc(i,k), for z faces gc(i,j) (reference:

@@ -42,6 +42,8 @@ def lib():
         L.orc_set_bc_faces.argtypes = [_P, _I, _LP, _IP, _DP, C.c_longlong]
         L.orc_get_box.argtypes = [_P, _I, _I, _DP]
         L.orc_set_box.argtypes = [_P, _I, _I, _DP]
+        L.orc_max_abs.argtypes = [_P, _I]
+        L.orc_max_abs.restype = _D
         L.orc_fas_vcycle.argtypes = [_P, _I, _I, C.POINTER(_D), _I]
         L.orc_fas_fmg.argtypes = [_P, _I, _I, C.POINTER(_D)]
         for f in ("orc_apply_op",):
@@ -136,7 +138,14 @@ class Oracle:
 
     def get_level(self, lvl, iv, ids=None):
         ids = self.tree.lvls[lvl].ids if ids is None else ids
-        return np.stack([self.get_box(i, iv) for i in ids]) if len(ids) else None
+        if not len(ids):
+            return None
+        s = self.tree.box_size_lvl[lvl] + 2
+        out = np.empty((len(ids), s, s, s))   # (each box written in place: no copy per box)
+        flat = out.reshape(len(ids), -1)
+        for n, i in enumerate(ids):
+            self.L.orc_get_box(self.h, int(i), iv, flat[n])
+        return out
 
     def set_level(self, lvl, iv, data, ids=None):
         ids = self.tree.lvls[lvl].ids if ids is None else ids

@@ -198,13 +198,25 @@ CONFIGS = {
     "cyc_coarse_gs_rel": ("8 32 32 32 3 v gs:2:2:1000:1e-8:0.5 lpl 0 d0 sol 1 lb 1", True, [1]),
     "cyc_coarse_vlpl_gs_default": ("8 32 32 32 3 v gs vlpl 0 d0 sol 1 lb 1", True, [1]),
     "cyc_coarse_vlpl_gs_cap2": ("8 32 32 32 3 v gs:2:2:2 vlpl 0 d0 sol 1 lb 1", True, [1]),
+    # cycle "a" (omg_golden.f90): per iteration mg_fas_vcycle(highest_lvl =
+    # top - 1), mg_fas_vcycle(standalone = .false.), mg_restrict_lvl(rhs, top),
+    # mg_prolong(top - 1, phi -> old, add = .false.), mg_fill_ghost_cells_lvl(top,
+    # res), mg_fas_vcycle(max_res); a history line after each cycle, final phi
+    # and rhs of every box, and (mid_sha256) rhs, old and res of every box with
+    # their face ghosts right after the three calls of the last iteration,
+    # which no cycle's output shows: the entry points tests/apiwalk.py drives
+    # from outside, pinned to the reference
+    "api_per32_box8": ("8 32 32 32 3 a gsrb lpl 0 per sol 1 lb 0", True, [1, 2]),
+    "api_ref3_gs_box8": ("8 32 32 32 3 a gs lpl 0 sol sol 3 lb 0", True, [1, 3]),
+    "api_mx2_helm64_box16": ("16 64 64 64 2 a gsrb helm 2 mx2 sol 1 lb 0", True, [1]),
 }
 
 
-def read_rank_dumps(fn):
+def read_rank_dumps(fn, sized=False):
     """The multi-rank dump (omg_golden.f90 dump_phi_rank: <fn>.r<rank>, per
     owned box int32 lvl, int32 position in lvls(lvl)%ids, int32 nc, nc^3
-    doubles) in the one-rank file's order: levels lowest first, ids order."""
+    doubles) in the one-rank file's order: levels lowest first, ids order.
+    sized (dump_mid): the third integer is the box's number of doubles."""
     boxes = []
     for f in glob.glob(fn + ".r*"):
         b = open(f, "rb").read()
@@ -212,8 +224,9 @@ def read_rank_dumps(fn):
         while o < len(b):
             lvl, n, nc = struct.unpack_from("<3i", b, o)
             o += 12
-            boxes.append(((lvl, n), b[o:o + 8 * nc ** 3]))
-            o += 8 * nc ** 3
+            nd = nc if sized else nc ** 3
+            boxes.append(((lvl, n), b[o:o + 8 * nd]))
+            o += 8 * nd
     boxes.sort(key=lambda x: x[0])
     if len(set(k for k, _ in boxes)) != len(boxes):
         raise RuntimeError("a box was dumped by two ranks")
@@ -281,6 +294,20 @@ def main():
                     key = "rhs_sha256" if " ahelm " in args else "phi_sha256"
                     run_entry[key] = hashlib.sha256(b).hexdigest()
                     run_entry["phi_bytes"] = len(b)
+                    if args.split()[5] == "a":   # (its rhs too: <dump>_rhs)
+                        if r == 1:
+                            with open(fn + "_rhs", "rb") as f:
+                                b = f.read()
+                        else:
+                            b = read_rank_dumps(fn + "_rhs")
+                        run_entry["rhs_sha256"] = hashlib.sha256(b).hexdigest()
+                        # (and what its three calls between the cycles wrote: <dump>_mid)
+                        if r == 1:
+                            with open(fn + "_mid", "rb") as f:
+                                b = f.read()
+                        else:
+                            b = read_rank_dumps(fn + "_mid", sized=True)
+                        run_entry["mid_sha256"] = hashlib.sha256(b).hexdigest()
             entry["runs"][str(r)] = run_entry
             print(name, r, its[-1]["err"], its[-1]["res"], file=sys.stderr)
         golden[name] = entry

@@ -208,6 +208,12 @@ class OracleBackend:
     def fmg(self, have_guess, want):
         return self.o.fas_fmg(have_guess, bool(want))
 
+    def vcycle_to(self, highest_lvl, want, standalone):
+        return self.o.fas_vcycle(highest_lvl, bool(want), bool(standalone))
+
+    def call(self, name, *args):
+        getattr(self.o, name)(*args)
+
     def diffusion(self, order, dt):
         op = OPS[self.cfg["op"]]
         rc, n, res = self.o.diffusion_solve(op, dt, diffusion_coeff(self.cfg), order, DIFF_TOL)
@@ -299,6 +305,12 @@ class DeviceBackend:
 
     def fmg(self, have_guess, want):
         return omg.mg_fas_fmg(self.mg, have_guess, max_res=bool(want)) or 0.0
+
+    def vcycle_to(self, highest_lvl, want, standalone):
+        return omg.mg_fas_vcycle(self.mg, highest_lvl, max_res=bool(want), standalone=bool(standalone)) or 0.0
+
+    def call(self, name, *args):
+        self.mg.ctx.call(name, *args)
 
     def diffusion(self, order, dt):
         op = self.cfg["op"]
@@ -426,6 +438,49 @@ def phi_digest(be, iv=None):
     return h.hexdigest()
 
 
+def _owned(be, lvl):
+    """(ids, download) of the boxes of a level this backend holds: a rank's own
+    (a replicated coarse level: every box, each rank holds them all)."""
+    if isinstance(be, OracleBackend):
+        return be.my_ids(lvl), be.get_level
+    n, _ = be.mg.ctx.level_size(lvl)
+    ids = be.my_ids(lvl)
+    if lvl <= be.rep_lvl and n == len(be.tree.lvls[lvl].ids):
+        ids = be.tree.lvls[lvl].ids
+    return (ids if n else []), be.mg.get_level
+
+
+def mid_boxes(be):
+    """omg_golden's dump_mid: {(lvl, id): bytes} of rhs, old and res of every
+    box held, each the interior and then the face ghosts x-, x+, y-, y+, z-,
+    z+ (arrays [k, j, i])."""
+    out = {}
+    for lvl in be.levels():
+        ids, get = _owned(be, lvl)
+        if not len(ids):
+            continue
+        nc = be.tree.box_size_lvl[lvl]
+        c, lo, hi = slice(1, nc + 1), 0, nc + 1
+        parts = {iv: get(lvl, iv) for iv in (T.MG_IRHS, T.MG_IOLD, T.MG_IRES)}
+        for q, id_ in enumerate(ids):
+            b = []
+            for iv in (T.MG_IRHS, T.MG_IOLD, T.MG_IRES):
+                a = parts[iv][q]
+                b += [a[c, c, c], a[c, c, lo], a[c, c, hi], a[c, lo, c], a[c, hi, c], a[lo, c, c], a[hi, c, c]]
+            out[(lvl, int(id_))] = b"".join(np.ascontiguousarray(x).tobytes() for x in b)
+    return out
+
+
+def boxes_digest(tree, boxes):
+    """sha256 over {(lvl, id): bytes} in the one-rank order (levels lowest
+    first, ids order)."""
+    h = hashlib.sha256()
+    for lvl in range(tree.lowest_lvl, tree.highest_lvl + 1):
+        for id_ in tree.lvls[lvl].ids:
+            h.update(boxes[(lvl, int(id_))])
+    return h.hexdigest()
+
+
 class StepError(RuntimeError):
     """A step that failed the way the reference's error stop does; .history
     holds what was printed before it."""
@@ -465,6 +520,21 @@ def _tree_cycles(be, cfg, reduce=None):
                 raise StepError(str(ex), hist) from ex
             record(n, 0.0)
             continue
+        if cfg["cycle"] == "a":
+            # omg_golden's script of the calls a caller makes between cycles:
+            # a history line after each of its three cycles
+            hi = be.tree.highest_lvl
+            be.vcycle_to(hi - 1, False, True)
+            record(n, 0.0)
+            be.vcycle_to(None, False, False)
+            record(n, 0.0)
+            be.call("restrict_lvl", T.MG_IRHS, hi)
+            be.call("prolong", hi - 1, T.MG_IPHI, T.MG_IOLD, 0)
+            be.call("fill_ghost_cells_lvl", hi, T.MG_IRES)
+            if n == cfg["n_its"]:   # omg_golden's dump_mid: what the three calls wrote
+                be.mid = mid_boxes(be)
+            record(n, be.vcycle(True))
+            continue
         if cfg["cycle"] == "f":
             m = be.fmg(n > 1, cfg["maxres"])
         else:
@@ -487,8 +557,10 @@ def run_problem(args: str, backend="device", n_ranks=1, n_its=None, reduce=None)
     except StepError as ex:   # the reference's error stop: what it printed + the message
         return {"history": ex.history, "error": str(ex), "backend": be}
     out = {"history": hist, "phi_sha256": phi_digest(be), "backend": be}
-    if cfg["op"] == "ahelm":
+    if cfg["op"] == "ahelm" or cfg["cycle"] == "a":
         out["rhs_sha256"] = phi_digest(be, T.MG_IRHS)
+    if cfg["cycle"] == "a":
+        out["mid_sha256"] = boxes_digest(be.tree, be.mid)
     return out
 
 
@@ -583,7 +655,7 @@ def run_problem_loopback(args: str, n_ranks: int, n_its=None, timeout=600, rep_c
         st = {name: be.mg.ctx.kernel_stats(name)[0] for name in stats}
         t = be.tree   # (copied: run_loopback frees the storage, which empties the level lists)
         order = [(lvl, [int(i) for i in t.lvls[lvl].ids]) for lvl in range(t.lowest_lvl, t.highest_lvl + 1)]
-        return hist, _owned_phi(be), (order, t.rank.copy()), st
+        return hist, _owned_phi(be), (order, t.rank.copy()), st, getattr(be, "mid", None)
 
     res = run_loopback(args, n_ranks, body, n_its, timeout, rep_cells)
     out = [r[0] for r in res]
@@ -596,4 +668,14 @@ def run_problem_loopback(args: str, n_ranks: int, n_its=None, timeout=600, rep_c
             key = (lvl, id_)
             owner = int(owners[id_])
             h.update(phis[owner][key] if key in phis[owner] else phis[0][key])
-    return {"history": out[0], "phi_sha256": h.hexdigest(), "stats": [r[3] for r in res]}
+    ret = {"history": out[0], "phi_sha256": h.hexdigest(), "stats": [r[3] for r in res]}
+    if cfg["cycle"] == "a":   # (the same gathering, in the same order)
+        hm = hashlib.sha256()
+        mids = [r[4] for r in res]
+        for lvl, ids in order:
+            for id_ in ids:
+                key = (lvl, id_)
+                owner = int(owners[id_])
+                hm.update(mids[owner][key] if key in mids[owner] else mids[0][key])
+        ret["mid_sha256"] = hm.hexdigest()
+    return ret

@@ -26,11 +26,10 @@ import json
 import os
 import random
 
-import numpy as np
 import pytest
 
-from tests.mgdriver import (OPS, SOLVER_DEFAULTS, DeviceBackend, OracleBackend, _cycles, hexbits, measure, parse,
-                            phi_digest, setup_problem)
+from tests.apiwalk import Pair, _assert_same, _stored_mask  # noqa: F401  (the walk vocabulary lives there)
+from tests.mgdriver import SOLVER_DEFAULTS, DeviceBackend, _cycles, hexbits, measure, parse, phi_digest, setup_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -51,86 +50,6 @@ def _set_bound(monkeypatch, param):
     else:
         monkeypatch.delenv("OMG_BLOCK3_COLUMN", raising=False)
     return int(bound)
-
-
-def _stored_mask(nc):
-    s = nc + 2
-    ix = np.arange(s)
-    bnd = ((ix == 0) | (ix == s - 1)).astype(int)
-    return (bnd[:, None, None] + bnd[None, :, None] + bnd[None, None, :]) < 2
-
-
-def _assert_same(dev, orc, msg, ivs=(1, 2, 3, 4)):
-    for lvl in dev.levels():
-        if not len(dev.my_ids(lvl)):
-            continue
-        m = _stored_mask(dev.tree.box_size_lvl[lvl])
-        for iv in ivs:
-            a, b = dev.get_level(lvl, iv), orc.get_level(lvl, iv)
-            assert np.array_equal(a[:, m].view(np.uint64), b[:, m].view(np.uint64)), (lvl, iv, msg)
-
-
-class Pair:
-    """The device and the oracle over one problem, given every change alike."""
-
-    def __init__(self, args):
-        self.cfg = cfg = parse(args)
-        self.dev, self.orc = DeviceBackend(cfg), OracleBackend(cfg)
-        self.sub = cfg["bc"] == "per"
-        self.params = list(SOLVER_DEFAULTS)
-        for be in (self.dev, self.orc):
-            setup_problem(be)
-
-    def set(self, cycles=None, coarse=None, oracle_cycles=None):
-        import pyoracle  # on sys.path once OracleBackend exists (checker only)
-        if cycles is not None:
-            self.params[:2] = cycles
-        if coarse is not None:
-            self.params[2:] = coarse
-        down, up, cmax, cabs, crel = self.params
-        mg = self.dev.mg
-        mg.n_cycle_down, mg.n_cycle_up = down, up
-        mg.max_coarse_cycles, mg.residual_coarse_abs, mg.residual_coarse_rel = cmax, cabs, crel
-        mg._push_methods()
-        if oracle_cycles is not None:
-            down, up = oracle_cycles
-        sm = pyoracle.GSRB if self.cfg["smoother"] == "gsrb" else pyoracle.GS
-        self.orc.o.configure(op=OPS[self.cfg["op"]], lam=self.cfg["lam"], smoother=sm, n_cycle_down=down,
-                             n_cycle_up=up, max_coarse_cycles=cmax, res_abs=cabs, res_rel=crel,
-                             subtract_mean=self.sub)
-
-    def step(self, step, msg):
-        dev, orc = self.dev, self.orc
-        kind = step[0]
-        if kind == "vcycle":
-            assert dev.vcycle(step[1]) == orc.vcycle(step[1]), msg
-        elif kind == "fmg":
-            assert dev.fmg(True, True) == orc.fmg(True, True), msg
-        elif kind == "counts":
-            self.set(cycles=step[1])
-        elif kind == "apply_op":
-            dev.apply_op(4); orc.apply_op(4)
-        elif kind == "fill":
-            dev.fill_ghost_cells(1); orc.fill_ghost_cells(1)
-        elif kind == "upload":
-            # another phi, interior and ghosts (the ghosts no fill's result)
-            for lvl in dev.levels():
-                if len(dev.my_ids(lvl)):
-                    a = 0.5 * orc.get_level(lvl, 1)
-                    dev.set_level(lvl, 1, a); orc.set_level(lvl, 1, a)
-        else:
-            raise ValueError(kind)
-
-    def run(self, steps, lazy=False):
-        """lazy: no comparison right after a cycle without the max residual
-        or a change of the counts.  The download is a reader of phi's ghosts
-        like any other and fills deferred ones first, so only then does the
-        cycle's deferral meet the step after it."""
-        for n, step in enumerate(steps):
-            msg = f"step {n} {step} of {steps}"
-            self.step(step, msg)
-            if not (lazy and (step == V0 or step[0] == "counts") and n + 1 < len(steps)):
-                _assert_same(self.dev, self.orc, msg)
 
 
 # -- a. the reference's runs, block passes under the lowered level bounds ------

@@ -35,6 +35,8 @@ def _check(out, run):
     assert out["history"] == run["history"]
     if "phi_sha256" in run:
         assert out["phi_sha256"] == run["phi_sha256"]
+    if "mid_sha256" in run:   # cycle a: what its calls between the cycles wrote
+        assert out["mid_sha256"] == run["mid_sha256"]
 
 
 @pytest.mark.parametrize("name,ranks", MULTI)

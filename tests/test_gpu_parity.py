@@ -28,6 +28,8 @@ def test_device_matches_reference_golden(name):
         assert out["phi_sha256"] == run["phi_sha256"]
     if "rhs_sha256" in run:   # aniso operator pinned through rhs = L(u)
         assert out["rhs_sha256"] == run["rhs_sha256"]
+    if "mid_sha256" in run:   # cycle a: what its calls between the cycles wrote
+        assert out["mid_sha256"] == run["mid_sha256"]
 
 
 def _random_fill(be, rng, ivs=(1, 2, 5)):

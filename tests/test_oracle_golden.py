@@ -62,3 +62,20 @@ def test_oracle_matches_reference(name, ranks):
         assert out["phi_sha256"] == run["phi_sha256"]
     if "rhs_sha256" in run:   # aniso operator pinned through rhs = L(u)
         assert out["rhs_sha256"] == run["rhs_sha256"]
+    if "mid_sha256" in run:   # cycle a: what its calls between the cycles wrote
+        assert out["mid_sha256"] == run["mid_sha256"]
+
+
+# Cycle a's calls between the cycles (mg_restrict_lvl of rhs, mg_prolong into
+# old without adding, mg_fill_ghost_cells_lvl of res) show in nothing a cycle
+# prints or leaves in phi; mid_sha256 is what pins them.  Each of them left
+# out must change it.
+@pytest.mark.parametrize("skipped", ["restrict_lvl", "prolong", "fill_ghost_cells_lvl"])
+@pytest.mark.parametrize("name", ["api_per32_box8", "api_ref3_gs_box8"])
+def test_api_script_calls_show_in_the_golden(monkeypatch, name, skipped):
+    from tests.mgdriver import OracleBackend
+    call = OracleBackend.call
+    monkeypatch.setattr(OracleBackend, "call", lambda self, fn, *a: None if fn == skipped else call(self, fn, *a))
+    e = GOLDEN[name]
+    out = run_problem(e["args"], backend="oracle")
+    assert out["mid_sha256"] != e["runs"]["1"]["mid_sha256"]
