@@ -163,6 +163,48 @@ int omg_level_size(omg_ctx *ctx, int lvl, int *n_boxes, int *nc);
 int omg_upload_level(omg_ctx *ctx, int lvl, int iv, const double *host);
 int omg_download_level(omg_ctx *ctx, int lvl, int iv, double *host);
 
+/* Stream-ordered dense device I/O (no reference counterpart; no staging
+ * buffer, and no host synchronise except as the last paragraph says).  A dense window of level lvl's cell grid,
+ * in DEVICE memory of the context's GPU: element (x,y,z), 0 <= x < n[0] etc.,
+ * is dev[x*stride[0] + y*stride[1] + z*stride[2]] and is the cell whose
+ * 0-based global index at lvl is lo + (x,y,z) (box ix, local i ->
+ * (ix-1)*nc + (i-1)).  stride[0] must be 1, stride[1] >= n[0], stride[2] >=
+ * stride[1]*n[1].  What moves: the interior cells of this rank's boxes at lvl
+ * that fall inside the window.  Ghost slots are never read or written (a put
+ * into rhs keeps what omg_phi_bc_store stored there); on put, cells outside
+ * the window keep their values; on get, window elements that no box of this
+ * rank covers keep theirs.  The window may be smaller than the level, cut
+ * through boxes or reach outside the domain (no periodic wrap).
+ * *n_cells (if non-NULL) = the cells copied, counted on the host from the box
+ * table; a plan-only context (OMG_DEVICE_NONE) validates, counts and copies
+ * nothing.
+ * stream: the caller's hipStream_t (NULL: the null stream).  The copy runs on
+ * omg_stream(ctx) after the work already queued on `stream`, and work queued
+ * on `stream` afterwards runs after the copy.
+ * State: omg_put_dense is a writer like omg_upload_level (pending work on phi
+ * is applied first, derived copies of rhs are dropped, a put of phi makes the
+ * level's ghosts stale and is collective in the same sense); it leaves the
+ * ghost cells as they are, so after a put of phi they are those of the old
+ * phi until the next fill.  omg_get_dense reads like omg_download_level, the
+ * host's own boxes on a replicated level; omg_put_dense refuses a replicated
+ * level (use omg_upload_level).  Errors (nothing is launched): a bad lvl, iv,
+ * extent or stride, a NULL pointer with a non-empty window, a pointer that is
+ * not device memory of the context's GPU.
+ * Environment, read per call: OMG_DENSE_GENERIC=1 the per-cell kernel for
+ * every box (A/B timing and cross-checks).
+ * The clipping of the boxes against a window is kept per level for the four
+ * most recent windows (a window: lo, n, stride, whether the base is 16-B
+ * aligned, the switch above).  A call with one of them uploads nothing and
+ * never waits on the host; a new window uploads its records from pinned
+ * memory in stream order; a fifth distinct window on a level replaces the
+ * oldest, and that call waits for the context's stream first. */
+int omg_put_dense(omg_ctx *ctx, int lvl, int iv, const double *dev, const long long lo[3],
+                  const long long n[3], const long long stride[3], void *stream,
+                  long long *n_cells);
+int omg_get_dense(omg_ctx *ctx, int lvl, int iv, double *dev, const long long lo[3],
+                  const long long n[3], const long long stride[3], void *stream,
+                  long long *n_cells);
+
 /* The hot path.  omg_fas_vcycle = mg_fas_vcycle (src/m_multigrid.f90:150-243);
  * highest_lvl < lowest_lvl means "not present".  omg_fas_fmg = mg_fas_fmg
  * (:84-147).  max_res is written when want_max_res (the optional argument). */

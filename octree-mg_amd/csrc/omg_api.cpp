@@ -53,6 +53,163 @@ double* stage(omg_ctx* c, size_t n) {
   return c->d_stage;
 }
 
+// --- dense device I/O (omg_put_dense / omg_get_dense, kernels: omg_dense.hip)
+constexpr long long kDenseMax = 1LL << 40;   // bound on |lo|, n and the strides (no overflow below)
+
+// The clip records of a window, from the level's cache or built now.  aligned:
+// the window's base is 16-B aligned; generic: the per-cell kernel for every
+// box; own_only: the host's own partition of a replicated level.
+DensePlan& dense_plan(omg_ctx* c, Level& L, const long long* lo, const long long* n, const long long* stride,
+                      bool aligned, bool generic, bool own_only) {
+  for (auto& P : L.dense)
+    if (std::equal(lo, lo + 3, P.lo) && std::equal(n, n + 3, P.n) && std::equal(stride, stride + 3, P.stride) &&
+        P.aligned == aligned && P.generic == generic && P.own_only == own_only) {
+      P.age = ++c->dense_age;
+      return P;
+    }
+  if ((int)L.dense.size() < kDensePlans) L.dense.emplace_back();
+  DensePlan& P = *std::min_element(L.dense.begin(), L.dense.end(),
+                                   [](const DensePlan& a, const DensePlan& b) { return a.age < b.age; });
+  // (the oldest window makes room: its records may still be on their way to
+  // the device or being read there; the only host wait of the dense entries)
+  if (P.d_clips) host_sync(c, c->stream);
+  std::copy(lo, lo + 3, P.lo);
+  std::copy(n, n + 3, P.n);
+  std::copy(stride, stride + 3, P.stride);
+  P.aligned = aligned;
+  P.generic = generic;
+  P.own_only = own_only;
+  P.age = ++c->dense_age;
+  P.n_row = P.n_gen = 0;
+  P.n_cells = 0;
+  std::vector<DenseClip> row, gen;
+  const long long nc = L.nc;
+  const bool row_ok = !generic && aligned && dense_row_nc(L.nc) && stride[1] % 2 == 0 && stride[2] % 2 == 0;
+  auto clip = [&](int b) {
+    DenseClip r{};
+    r.box = b;
+    int* lohi[3][2] = {{&r.i0, &r.i1}, {&r.j0, &r.j1}, {&r.k0, &r.k1}};
+    long long cells = 1;
+    for (int d = 0; d < 3; d++) {
+      const long long g0 = ((long long)c->ix[(size_t)(L.ids[b] - 1) * 3 + d] - 1) * nc;   // global index of local cell 1
+      const long long a = std::max(g0, lo[d]), e = std::min(g0 + nc, lo[d] + n[d]);
+      if (a >= e) return;
+      *lohi[d][0] = (int)(a - g0) + 1;
+      *lohi[d][1] = (int)(e - g0);
+      r.off += (a - lo[d]) * stride[d];
+      cells *= e - a;
+    }
+    P.n_cells += cells;
+    (row_ok && r.i0 == 1 && r.i1 == L.nc && r.off % 2 == 0 ? row : gen).push_back(r);
+  };
+  if (own_only)
+    for (int b : L.host_local) clip(b);
+  else
+    for (int b = 0; b < L.n; b++) clip(b);
+  P.n_row = (int)row.size();
+  P.n_gen = (int)gen.size();
+  row.insert(row.end(), gen.begin(), gen.end());
+  if (!c->host_only && !row.empty()) {
+    if (row.size() > P.cap) {
+      dfree(P.d_clips);
+      if (P.h_clips) HIPCHK(hipHostFree(P.h_clips));
+      P.h_clips = nullptr;
+      P.cap = 0;
+      HIPCHK(hipHostMalloc((void**)&P.h_clips, sizeof(DenseClip) * row.size()));
+      HIPCHK(hipMalloc(&P.d_clips, sizeof(DenseClip) * row.size()));
+      P.cap = row.size();
+    }
+    // from pinned memory, in stream order ahead of the kernel: no host wait
+    // (the pinned copy is rewritten only after the wait above)
+    std::copy(row.begin(), row.end(), P.h_clips);
+    HIPCHK(hipMemcpyAsync(P.d_clips, P.h_clips, sizeof(DenseClip) * row.size(), hipMemcpyHostToDevice, c->stream));
+  }
+  return P;
+}
+
+void dense_io(omg_ctx* c, int lvl, int iv, double* dev, const long long* lo, const long long* n,
+              const long long* stride, void* stream, long long* n_cells, bool put) {
+  const char* who = put ? "omg_put_dense" : "omg_get_dense";
+  auto fail = [&](const std::string& what) { throw OmgError(std::string(who) + ": " + what); };
+  Level* L = level_ptr(c, lvl);
+  if (!L) fail("no such level");
+  if (iv < 1 || iv > c->n_vars) fail("bad variable index");
+  if (!lo || !n || !stride) fail("lo, n and stride are required");
+  for (int d = 0; d < 3; d++) {
+    if (n[d] < 0) fail("negative extent");
+    if (n[d] > kDenseMax || lo[d] > kDenseMax || lo[d] < -kDenseMax || stride[d] > kDenseMax)
+      fail("window out of range");
+  }
+  if (stride[0] != 1) fail("stride[0] must be 1");
+  const bool empty = n[0] == 0 || n[1] == 0 || n[2] == 0;
+  if (!empty) {
+    if (stride[1] < n[0]) fail("stride[1] < n[0]");
+    if (stride[2] / n[1] < stride[1]) fail("stride[2] < stride[1]*n[1]");
+    if (stride[2] > LLONG_MAX / 8 / n[2]) fail("window out of range");
+    if (!dev) fail("NULL pointer with a non-empty window");
+  }
+  if (put && L->replicated)
+    fail("level " + std::to_string(lvl) + " is replicated on every rank: use omg_upload_level");
+  const bool generic = env_flag("OMG_DENSE_GENERIC");
+  const bool aligned = ((uintptr_t)dev & 15) == 0;
+  if (c->host_only) {
+    if (n_cells) *n_cells = empty ? 0 : dense_plan(c, *L, lo, n, stride, aligned, generic, L->replicated).n_cells;
+    return;
+  }
+  if (!empty) {
+    // the pointer must be device memory of this GPU, the window inside its allocation
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, dev) != hipSuccess) {
+      (void)hipGetLastError();
+      fail("the pointer is not device memory");
+    }
+    if (at.type != hipMemoryTypeDevice) fail("the pointer is not device memory");
+    if (at.device != c->device) fail("the pointer belongs to another GPU than the context's");
+    hipDeviceptr_t base = nullptr;
+    size_t bytes = 0;
+    if (hipMemGetAddressRange(&base, &bytes, (hipDeviceptr_t)dev) == hipSuccess) {
+      const long long extent = (n[2] - 1) * stride[2] + (n[1] - 1) * stride[1] + n[0];
+      if ((const char*)dev + (size_t)extent * sizeof(double) > (const char*)base + bytes)
+        fail("the window reaches past the end of the pointer's allocation");
+    } else {
+      (void)hipGetLastError();
+    }
+  }
+  if (put) {
+    enter(c);
+    // (before the early return, as omg_upload_level)
+    if (iv == 1) phi_dirty(c, lvl);
+  } else {
+    enter(c, false);
+  }
+  if (n_cells) *n_cells = 0;
+  if (empty || !L->n) return;
+  DensePlan& P = dense_plan(c, *L, lo, n, stride, aligned, generic, L->replicated);
+  if (n_cells) *n_cells = P.n_cells;
+  if (!P.n_cells) return;
+  if ((long long)P.n_gen * 16 > INT_MAX) fail("too many boxes for one launch");
+  hipStream_t user = (hipStream_t)stream;
+  const bool foreign = user != c->stream;
+  if (foreign) {
+    HIPCHK(hipEventRecord(c->ev_dense_in, user));
+    HIPCHK(hipStreamWaitEvent(c->stream, c->ev_dense_in, 0));
+  }
+  {
+    Prof p(c, put ? "dense_put" : "dense_get", (double)P.n_cells, lvl);
+    const LevelView V = L->view();
+    if (P.n_row) {
+      Prof pr(c, put ? "dense_put_row" : "dense_get_row", (double)P.n_row * L->nc * L->nc * L->nc, lvl);
+      launch_dense_row(V, iv, P.d_clips, P.n_row, dev, stride[1], stride[2], put, c->stream);
+    }
+    launch_dense_cell(V, iv, P.d_clips + P.n_row, P.n_gen, dev, stride[1], stride[2], put, c->stream);
+    HIPCHK(hipGetLastError());
+  }
+  if (foreign) {
+    HIPCHK(hipEventRecord(c->ev_dense_out, c->stream));
+    HIPCHK(hipStreamWaitEvent(user, c->ev_dense_out, 0));
+  }
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -185,6 +342,8 @@ int omg_ctx_create(omg_ctx** out, int device, int rank, int n_ranks, const void*
     HIPCHK(hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->ev_side, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->ev_phi, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_dense_in, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_dense_out, hipEventDisableTiming));
     HIPCHK(hipHostMalloc(&c->h_scalar, sizeof(double) * (16 + (size_t)n_ranks)));
     for (int iv = 0; iv < kMaxVars; iv++)
       for (int nb = 0; nb < 6; nb++) {
@@ -224,6 +383,8 @@ int omg_ctx_destroy(omg_ctx* c) {
     if (c->ev_main) (void)hipEventDestroy(c->ev_main);
     if (c->ev_side) (void)hipEventDestroy(c->ev_side);
     if (c->ev_phi) (void)hipEventDestroy(c->ev_phi);
+    if (c->ev_dense_in) (void)hipEventDestroy(c->ev_dense_in);
+    if (c->ev_dense_out) (void)hipEventDestroy(c->ev_dense_out);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
     if (c->stream_comm) (void)hipStreamDestroy(c->stream_comm);
     if (c->ev_bnd) (void)hipEventDestroy(c->ev_bnd);
@@ -475,6 +636,16 @@ int omg_download_level(omg_ctx* c, int lvl, int iv, double* host) {
     HIPCHK(hipMemcpyAsync(host, st, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
     host_sync(c, c->stream);
   });
+}
+
+int omg_put_dense(omg_ctx* c, int lvl, int iv, const double* dev, const long long* lo, const long long* n,
+                  const long long* stride, void* stream, long long* n_cells) {
+  return guarded([&] { dense_io(c, lvl, iv, const_cast<double*>(dev), lo, n, stride, stream, n_cells, true); });
+}
+
+int omg_get_dense(omg_ctx* c, int lvl, int iv, double* dev, const long long* lo, const long long* n,
+                  const long long* stride, void* stream, long long* n_cells) {
+  return guarded([&] { dense_io(c, lvl, iv, dev, lo, n, stride, stream, n_cells, false); });
 }
 
 int omg_fas_vcycle(omg_ctx* c, int highest_lvl, int want_max_res, double* max_res, int standalone) {

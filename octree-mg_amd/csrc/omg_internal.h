@@ -111,6 +111,31 @@ struct RbHostFaces {
   double* h_cc = nullptr;    // pinned
 };
 
+// Dense device I/O (omg_put_dense / omg_get_dense, omg_dense.hip): one record
+// per box that a window of the level's cell grid covers: the local box, the
+// covered local cells [i0,i1] x [j0,j1] x [k0,k1] (1-based) and the offset in
+// the window, in doubles, of cell (i0, j0, k0).
+struct DenseClip {
+  int box;
+  int i0, i1, j0, j1, k0, k1;
+  int pad_;
+  long long off;
+};
+
+// The records of one window, cached on the level: the boxes the row kernel
+// serves first (n_row), then those of the per-cell kernel (n_gen).
+struct DensePlan {
+  long long lo[3] = {0, 0, 0}, n[3] = {0, 0, 0}, stride[3] = {0, 0, 0};
+  bool aligned = false, generic = false, own_only = false;   // (part of the key)
+  DenseClip* h_clips = nullptr;     // pinned: the source of the stream-ordered upload
+  DenseClip* d_clips = nullptr;
+  size_t cap = 0;                   // records h_clips and d_clips hold
+  int n_row = 0, n_gen = 0;
+  long long n_cells = 0;
+  long long age = 0;                // last use (the oldest entry is replaced)
+};
+constexpr int kDensePlans = 4;
+
 struct Level {
   int lvl = 0, nc = 0, n = 0;
   long long stride = 0;
@@ -236,6 +261,7 @@ struct Level {
   // per-leaf partial sums scratch
   double* d_scratch = nullptr;
   std::map<int, RbHostFaces> rbh;    // by variable: faces with a host refinement_bnd callback
+  std::vector<DensePlan> dense;      // windows of omg_put_dense / omg_get_dense (at most kDensePlans)
 
   LevelView view() const {
     LevelView v;
@@ -337,6 +363,8 @@ struct omg_ctx {
   int comm_priority = 0;               // its priority (hipDeviceGetStreamPriorityRange's greatest)
   hipEvent_t ev_bnd = nullptr, ev_comm = nullptr;
   hipEvent_t ev_main = nullptr, ev_side = nullptr, ev_phi = nullptr;
+  hipEvent_t ev_dense_in = nullptr, ev_dense_out = nullptr;   // omg_put_dense / omg_get_dense: the caller's stream
+  long long dense_age = 0;
   bool phi_mean_on_side = false;
   bool no_tail = false;                // OMG_NO_TAIL: level-by-level coarse end (A/B checks)
   bool no_fuse_up = false;             // OMG_NO_FUSE_UP: separate prolongation and first up-substep

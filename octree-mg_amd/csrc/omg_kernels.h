@@ -180,6 +180,15 @@ void launch_copy_var(const LevelView& L, int src, int dst, hipStream_t st);
 void launch_from_ref(const LevelView& L, int iv, const double* ref, hipStream_t st);
 void launch_to_ref(const LevelView& L, int iv, double* ref, double unstored, hipStream_t st);
 void launch_poison_ghosts(const LevelView& L, int n_vars, double poison, hipStream_t st);
+// dense device I/O (omg_dense.hip): variable iv's interior cells <-> a dense
+// window [z][y][x] (strides 1, s1, s2 doubles) by clip records (DenseClip);
+// the row kernel takes boxes of dense_row_nc() sizes whose covered rows are
+// whole in x and 16-B aligned in the window, the cell kernel anything
+bool dense_row_nc(int nc);
+void launch_dense_row(const LevelView& L, int iv, const DenseClip* clips, int n, double* dense, long long s1,
+                      long long s2, bool put, hipStream_t st);
+void launch_dense_cell(const LevelView& L, int iv, const DenseClip* clips, int n, double* dense, long long s1,
+                       long long s2, bool put, hipStream_t st);
 void launch_phi_bc_store(const LevelView& L, const GcBC& bc, int* nba, hipStream_t st);
 
 // The coarse end of the V-cycle in ONE single-workgroup launch (omg_tiles.hip):

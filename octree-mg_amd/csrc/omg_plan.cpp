@@ -201,6 +201,11 @@ void free_levels(omg_ctx* c) {
     dfree(L.d_galt);
     dfree(L.d_phi_buf); dfree(L.d_b3); dfree(L.d_b3c); L.n_b3 = 0; L.h_b3.clear();
     dfree(L.d_physbox);
+    for (auto& P : L.dense) {
+      dfree(P.d_clips);
+      if (P.h_clips) (void)hipHostFree(P.h_clips);
+    }
+    L.dense.clear();
     dfree(L.d_rbsend); dfree(L.d_rbrecv); dfree(L.d_bnd); dfree(L.d_int); dfree(L.d_push0); dfree(L.d_bndface);
     for (Transfer* T : {&L.halo, &L.restr, &L.prol, &L.rbx, &L.repl, &L.deep_phi, &L.deep_rhs}) {
       dfree(T->d_send_items);

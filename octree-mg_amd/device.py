@@ -42,6 +42,8 @@ SIGNATURES = {
     "omg_level_size": (_I, [_P, _I, C.POINTER(_I), C.POINTER(_I)]),
     "omg_upload_level": (_I, [_P, _I, _I, _DP]),
     "omg_download_level": (_I, [_P, _I, _I, _DP]),
+    "omg_put_dense": (_I, [_P, _I, _I, C.c_void_p, _LP, _LP, _LP, C.c_void_p, C.POINTER(_LL)]),
+    "omg_get_dense": (_I, [_P, _I, _I, C.c_void_p, _LP, _LP, _LP, C.c_void_p, C.POINTER(_LL)]),
     "omg_fas_vcycle": (_I, [_P, _I, _I, C.POINTER(_D), _I]),
     "omg_fas_fmg": (_I, [_P, _I, _I, C.POINTER(_D)]),
     "omg_apply_op": (_I, [_P, _I]),
@@ -152,6 +154,7 @@ class Context:
         h = _P()
         check(self.L.omg_ctx_create(C.byref(h), device, rank, n_ranks, uid))
         self.h = h
+        self.device = device
 
     def close(self):
         if getattr(self, "h", None):
@@ -240,6 +243,25 @@ class Context:
         if n:
             self.call("download_level", lvl, iv, out)
         return out.reshape(n, nc + 2, nc + 2, nc + 2)
+
+    def _dense(self, name, lvl, iv, ptr, lo, n, stride, stream):
+        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64).reshape(3)  # noqa: E731
+        cells = _LL(0)
+        self.call(name, lvl, iv, C.c_void_p(int(ptr) or None), i64(lo), i64(n), i64(stride),
+                  C.c_void_p(int(stream) or None), C.byref(cells))
+        return cells.value
+
+    def put_dense(self, lvl, iv, ptr, lo, n, stride, stream=0):
+        """omg_put_dense: the dense window at device address ptr (x fastest:
+        lo, n, stride in x, y, z order, stride in doubles) into variable iv of
+        this rank's boxes at lvl, ordered behind the work queued on the
+        hipStream_t `stream` (0: the null stream).  Returns the cells copied."""
+        return self._dense("put_dense", lvl, iv, ptr, lo, n, stride, stream)
+
+    def get_dense(self, lvl, iv, ptr, lo, n, stride, stream=0):
+        """omg_get_dense: the reverse copy; window elements that no box of
+        this rank covers keep their values."""
+        return self._dense("get_dense", lvl, iv, ptr, lo, n, stride, stream)
 
     def scalar(self, name, *args):
         r = _D(0.0)

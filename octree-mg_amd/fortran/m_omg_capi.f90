@@ -17,6 +17,7 @@ module m_omg_capi
   public :: omg_tree_setup, omg_set_operator, omg_set_smoother
   public :: omg_set_subtract_mean, omg_set_bc, omg_set_bc_faces
   public :: omg_level_size, omg_upload_level, omg_download_level
+  public :: omg_put_dense, omg_get_dense
   public :: omg_fas_vcycle, omg_fas_fmg, omg_apply_op, omg_phi_bc_store
   public :: omg_synchronize, omg_diffusion_solve
   public :: omg_poisson_free_3d, omg_free_planes
@@ -163,6 +164,32 @@ module m_omg_capi
        real(c_double), intent(out) :: host(*)
        integer(c_int) :: ierr
      end function omg_download_level
+
+     ! omg_put_dense / omg_get_dense (include/omg.h): a dense window in device
+     ! memory.  dev (a device pointer) and stream (a hipStream_t, c_null_ptr =
+     ! the null stream) go by value; n_cells is c_loc of an integer(c_long_long)
+     ! target that receives the cells copied, or c_null_ptr
+     function omg_put_dense(ctx, lvl, iv, dev, lo, n, stride, stream, n_cells) &
+          bind(C, name="omg_put_dense") result(ierr)
+       import :: c_ptr, c_int, c_long_long
+       type(c_ptr), value               :: ctx
+       integer(c_int), value            :: lvl, iv
+       type(c_ptr), value               :: dev
+       integer(c_long_long), intent(in) :: lo(3), n(3), stride(3)
+       type(c_ptr), value               :: stream, n_cells
+       integer(c_int) :: ierr
+     end function omg_put_dense
+
+     function omg_get_dense(ctx, lvl, iv, dev, lo, n, stride, stream, n_cells) &
+          bind(C, name="omg_get_dense") result(ierr)
+       import :: c_ptr, c_int, c_long_long
+       type(c_ptr), value               :: ctx
+       integer(c_int), value            :: lvl, iv
+       type(c_ptr), value               :: dev
+       integer(c_long_long), intent(in) :: lo(3), n(3), stride(3)
+       type(c_ptr), value               :: stream, n_cells
+       integer(c_int) :: ierr
+     end function omg_get_dense
 
      function omg_fas_vcycle(ctx, highest_lvl, want_max_res, max_res, standalone) &
           bind(C, name="omg_fas_vcycle") result(ierr)

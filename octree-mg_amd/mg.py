@@ -50,6 +50,25 @@ _RB_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_
                      C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
 
 
+def dense_strides(t, what="dense"):
+    """(n, stride) in x, y, z order, in elements, of a tensor [nz, ny, nx] as
+    omg_put_dense / omg_get_dense take them, or ValueError: the last stride
+    must be 1, rows and planes in order and apart (no transposed, expanded or
+    overlapping view).  The stride of a dimension of size 1 is arbitrary in
+    torch, so it becomes the dense one."""
+    n = (t.shape[2], t.shape[1], t.shape[0])
+    sx = t.stride(2) if n[0] > 1 else 1
+    sy = t.stride(1) if n[1] > 1 else max(sx * n[0], 1)
+    sz = t.stride(0) if n[2] > 1 else max(sy * n[1], 1)
+    if t.numel():
+        if sx != 1:
+            raise ValueError(f"{what}: the last stride is {sx}, 1 is required")
+        if sy < n[0] or sz < sy * n[1]:
+            raise ValueError(f"{what}: strides {tuple(t.stride())} of shape {tuple(t.shape)}: "
+                             "stride(1) >= nx and stride(0) >= stride(1) * ny are required")
+    return n, (1, sy, sz)
+
+
 class MG(MGTree):
     """mg_t: tree (host) + device context (HIP)."""
 
@@ -89,6 +108,59 @@ class MG(MGTree):
     def get_level(self, lvl, iv):
         self._require_alloc()
         return self.ctx.download_level(lvl, iv)
+
+    def _dense_args(self, t, what):
+        """The checks of set_dense / get_dense on a tensor [nz, ny, nx], before
+        any call into the library; returns (n, stride) in x, y, z order."""
+        import torch
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise ValueError(f"{what}: a torch tensor [nz, ny, nx] is required")
+        if t.dtype != torch.float64:
+            raise ValueError(f"{what}: dtype {t.dtype}, torch.float64 is required")
+        n, stride = dense_strides(t, what)
+        if not t.is_cuda:
+            raise ValueError(f"{what}: the tensor is on {t.device}, not on the context's GPU")
+        self._require_alloc()
+        dev = self.ctx.device
+        if dev >= 0 and t.device.index != dev:
+            raise ValueError(f"{what}: the tensor is on {t.device}, the context on GPU {dev}")
+        return n, stride
+
+    def level_grid(self, lvl):
+        """(nx, ny, nz): the cell grid of level lvl over the whole domain."""
+        return tuple(int(v) for v in self.domain_size_lvl[lvl])
+
+    def set_dense(self, lvl, iv, tensor, lo=(0, 0, 0)):
+        """omg_put_dense: the torch.float64 tensor [nz, ny, nx] on the context's
+        GPU (the last stride 1, rows and planes in order and not
+        overlapping: stride(1) >= nx, stride(0) >= stride(1) * ny) is the window of level lvl's cell
+        grid that starts at the 0-based cell lo = (x, y, z); the interior cells
+        of this rank's boxes inside it take its values, ghost cells and cells
+        outside keep theirs.  Ordered on torch's current stream: no host
+        synchronisation.  Returns the number of cells copied."""
+        import torch
+        n, stride = self._dense_args(tensor, "set_dense")
+        return self.ctx.put_dense(lvl, iv, tensor.data_ptr(), lo, n, stride,
+                                  torch.cuda.current_stream(tensor.device).cuda_stream)
+
+    def get_dense(self, lvl, iv, out=None, lo=(0, 0, 0), shape=None):
+        """omg_get_dense into `out` [nz, ny, nx] (default: torch.empty of
+        shape = (nz, ny, nx), the level's whole cell grid from lo when None).
+        Elements that no box of this rank covers keep their values.  Returns
+        (out, cells copied)."""
+        import torch
+        if out is None:
+            self._require_alloc()
+            if shape is None:
+                g = self.level_grid(lvl)
+                shape = tuple(max(g[2 - q] - int(lo[2 - q]), 0) for q in range(3))
+            dev = self.ctx.device
+            out = torch.empty(tuple(int(v) for v in shape), dtype=torch.float64,
+                              device=torch.device("cuda", dev if dev >= 0 else torch.cuda.current_device()))
+        n, stride = self._dense_args(out, "get_dense")
+        cells = self.ctx.get_dense(lvl, iv, out.data_ptr(), lo, n, stride,
+                                   torch.cuda.current_stream(out.device).cuda_stream)
+        return out, cells
 
     def _require_alloc(self):
         if not self.is_allocated:
@@ -384,6 +456,16 @@ def mg_fill_ghost_cells_lvl(mg: MG, lvl, iv):
 
 def mg_prolong(mg: MG, lvl, iv, iv_to, add):
     mg.ctx.call("prolong", lvl, iv, iv_to, int(bool(add)))
+
+
+def mg_set_dense(mg: MG, lvl, iv, tensor, lo=(0, 0, 0)):
+    """MG.set_dense (omg_put_dense): a dense device tensor into variable iv."""
+    return mg.set_dense(lvl, iv, tensor, lo)
+
+
+def mg_get_dense(mg: MG, lvl, iv, out=None, lo=(0, 0, 0), shape=None):
+    """MG.get_dense (omg_get_dense): variable iv into a dense device tensor."""
+    return mg.get_dense(lvl, iv, out, lo, shape)
 
 
 def mg_phi_bc_store(mg: MG):
