@@ -309,6 +309,7 @@ int omg_ctx_create(omg_ctx** out, int device, int rank, int n_ranks, const void*
     c->no_block4p = env_flag("OMG_NO_BLOCK4P");
     c->block4_phys = env_flag("OMG_BLOCK4_PHYS");
     c->no_defer_gc = env_flag("OMG_NO_DEFER_GC");
+    c->no_rhs_pend = env_flag("OMG_NO_RHS_PEND");
     c->no_fuse_down_bc = env_flag("OMG_NO_FUSE_DOWN_BC");
     c->roctx = env_flag("OMG_ROCTX");
     c->debug = env_flag("OMG_DEBUG");
@@ -321,6 +322,8 @@ int omg_ctx_create(omg_ctx** out, int device, int rank, int n_ranks, const void*
     HIPCHK(hipMalloc(&c->d_scalar, sizeof(double) * (64 + 2 * (size_t)n_ranks)));
     HIPCHK(hipMalloc(&c->d_red, sizeof(double) * (8 + 2 * (size_t)n_ranks)));
     HIPCHK(hipMemset(c->d_red, 0, sizeof(double) * (8 + 2 * (size_t)n_ranks)));
+    HIPCHK(hipMalloc(&c->d_rhs_pend, sizeof(double) * (omg::kRhsPendMax + 1)));
+    HIPCHK(hipMemset(c->d_rhs_pend, 0, sizeof(double) * (omg::kRhsPendMax + 1)));
     HIPCHK(hipMalloc(&c->d_maxslots, sizeof(unsigned long long) * omg::kMaxSlots * omg::kMaxSlotStride));
     // (allocated here: no allocation may happen while a cycle is captured)
     HIPCHK(hipMalloc(&c->d_tail, sizeof(TailArgs)));
@@ -375,6 +378,7 @@ int omg_ctx_destroy(omg_ctx* c) {
     if (c->d_tail_stamps) (void)hipFree(c->d_tail_stamps);
     delete c->h_tail;
     dfree(c->d_red);
+    dfree(c->d_rhs_pend);
     dfree(c->d_maxslots);
     for (auto& kv : c->graphs)
       if (kv.second) (void)hipGraphExecDestroy(kv.second);
@@ -478,6 +482,9 @@ int omg_set_smoother(omg_ctx* c, int smoother, int n_cycle_down, int n_cycle_up,
   return guarded([&] {
     if (smoother != OMG_SMOOTHER_GS && smoother != OMG_SMOOTHER_GSRB)
       throw OmgError("unsupported smoother type");
+    if (smoother != c->smoother || std::max(n_cycle_down, 0) != c->n_cycle_down ||
+        std::max(n_cycle_up, 0) != c->n_cycle_up)
+      rhs_pend_retry(c);
     c->smoother = smoother;
     c->n_substeps = smoother == OMG_SMOOTHER_GSRB ? 2 : 1;
     ensure_rhs_lex(c);

@@ -625,11 +625,17 @@ constexpr int B4CX = kB3TX * B3H + 2 * B4CO, B4CY = B3H + 2 * B4CO, B4CT = B4CX 
 constexpr int B4CL = (B4CT + 63) / 64;   // coarse cells per lane of the loader wave
 constexpr int b4_threads(int pro) { return pro ? B4BS + 64 : B4BS; }
 
-template <int OP, int PRO, bool PHYS>
+// NS: the level's pending rhs mean shifts (RhsShifts), subtracted from every
+// rhs value at its load; a template parameter, so the loop holds exactly NS
+// subtractions per value and no branch (a run-time count's uniform branches
+// split the loop body and cost the correction form 76 us on C3's level 1)
+template <int OP, int PRO, bool PHYS, int NS>
 __global__ void __launch_bounds__(b4_threads(PRO)) k_gsrb4(LevelView L, double* __restrict__ dst,
                                                const int* __restrict__ cols, double lambda, int e,
                                                const double* __restrict__ shift, LevelView C,
-                                               const int* __restrict__ ccols, double fac, B3Phys P, int push) {
+                                               const int* __restrict__ ccols, double fac, B3Phys P, int push,
+                                               const double* __restrict__ rsh) {
+  static_assert(!(NS && PHYS), "k_gsrb4: no pending rhs shifts with physical faces");
   static_assert(PRO == 0 || PRO == 2, "k_gsrb4: plain or the correction from a stored coarse res");
   static_assert(!(PRO && PHYS), "k_gsrb4: physical faces in the plain form only");
   __shared__ double pl[2][4][B4PL];
@@ -846,6 +852,9 @@ __global__ void __launch_bounds__(b4_threads(PRO)) k_gsrb4(LevelView L, double* 
   const bool ctr = act && xs >= 1 && xs <= kB3TX && ys == 1;
   const int fi = ctr ? (j - 1) * B3CP + (xs - 1) * B3H + ih : 0;
   const double m = (!PRO && shift) ? *shift : 0.0;
+  // the level's pending rhs mean shifts: every thread subtracts them from the
+  // rhs values it loads, halo columns included (the same bits everywhere)
+  const RhsSubN<NS> rsub(rsh);
   // fac from the host (op_fac: the same expression, so the same bits): the
   // division on the device would hold it in VGPRs
   OpCoef<OP> K(L, lambda);
@@ -883,8 +892,9 @@ __global__ void __launch_bounds__(b4_threads(PRO)) k_gsrb4(LevelView L, double* 
   const int ci = act ? (p - 2 + B4CO) + B4CX * ((y >> 1) + B4CO) : B4CX + 1;
   auto step = [&](int t, double& q, double& fe, double& fo) {
     double ot = (!PRO && shift) ? b3_take(q) - m : b3_take(q);
-    const double ret = b3_take(fe), rot = b3_take(fo);
+    double ret = b3_take(fe), rot = b3_take(fo);
     load(t + AH, q, fe, fo);
+    rsub(ret, rot);
     if (PRO) {
       // phi += prolong(res) on the colour-(1-e) cell (prolong_at, as k_gsrb3)
       const int cz0 = t >> 1;
@@ -962,7 +972,7 @@ static double op_fac(const LevelView& L, int op, double lambda) {
 
 void launch_gsrb4(const LevelView& L, double* dst, const int* cols, int n_cols, int op, double lambda, int e,
                   const double* shift, hipStream_t st, const LevelView* coarse, const int* ccols,
-                  const B3Phys* phys, bool push) {
+                  const B3Phys* phys, bool push, RhsShifts rs) {
   const double fac = op_fac(L, op, lambda);
   if (n_cols <= 0) return;
   if (L.nc != B3NC) throw std::runtime_error("launch_gsrb4: box size must be 16");
@@ -971,19 +981,33 @@ void launch_gsrb4(const LevelView& L, double* dst, const int* cols, int n_cols, 
   if (phys && (coarse || shift))
     throw std::runtime_error("launch_gsrb4: physical faces in the plain form without a shift only");
   if (!push && phys) throw std::runtime_error("launch_gsrb4: physical faces need their ghosts written");
+  if (rs.n < 0 || rs.n > kRhsPendMax || (rs.n && (phys || !rs.s)))
+    throw std::runtime_error("launch_gsrb4: at most kRhsPendMax pending rhs shifts, none with physical faces");
   const LevelView& C = coarse ? *coarse : L;
   const B3Phys P = phys ? *phys : B3Phys{};
-#define OMG_B4(OPV, PMV, PHV, BS) \
-  k_gsrb4<OPV, PMV, PHV><<<n_cols, BS, 0, st>>>(L, dst, cols, lambda, e, shift, C, ccols, fac, P, push ? 1 : 0)
-  if (op == OP_HELM) {
-    if (coarse) OMG_B4(OP_HELM, 2, false, b4_threads(2));
-    else if (phys) OMG_B4(OP_HELM, 0, true, B4BS);
-    else OMG_B4(OP_HELM, 0, false, B4BS);
-  } else {
-    if (coarse) OMG_B4(OP_LPL, 2, false, b4_threads(2));
-    else if (phys) OMG_B4(OP_LPL, 0, true, B4BS);
-    else OMG_B4(OP_LPL, 0, false, B4BS);
+#define OMG_B4(OPV, PMV, PHV, NSV, BS)                                                                      \
+  k_gsrb4<OPV, PMV, PHV, NSV><<<n_cols, BS, 0, st>>>(L, dst, cols, lambda, e, shift, C, ccols, fac, P, push ? 1 : 0, \
+                                                     rs.s)
+  // (the instance with rs.n subtractions)
+#define OMG_B4N(OPV, PMV, BS)                                 \
+  switch (rs.n) {                                             \
+    case 0: OMG_B4(OPV, PMV, false, 0, BS); break;            \
+    case 1: OMG_B4(OPV, PMV, false, 1, BS); break;            \
+    case 2: OMG_B4(OPV, PMV, false, kRhsPendMax >= 2 ? 2 : 0, BS); break; \
+    case 3: OMG_B4(OPV, PMV, false, kRhsPendMax >= 3 ? 3 : 0, BS); break; \
+    default: OMG_B4(OPV, PMV, false, kRhsPendMax >= 4 ? 4 : 0, BS); break; \
   }
+  static_assert(kRhsPendMax >= 1 && kRhsPendMax <= 4, "launch_gsrb4 dispatches up to four pending shifts");
+  if (op == OP_HELM) {
+    if (coarse) OMG_B4N(OP_HELM, 2, b4_threads(2))
+    else if (phys) OMG_B4(OP_HELM, 0, true, 0, B4BS);
+    else OMG_B4N(OP_HELM, 0, B4BS)
+  } else {
+    if (coarse) OMG_B4N(OP_LPL, 2, b4_threads(2))
+    else if (phys) OMG_B4(OP_LPL, 0, true, 0, B4BS);
+    else OMG_B4N(OP_LPL, 0, B4BS)
+  }
+#undef OMG_B4N
 #undef OMG_B4
 }
 

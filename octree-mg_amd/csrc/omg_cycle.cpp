@@ -145,6 +145,7 @@ void fill_gc_lvl(omg_ctx* c, int lvl, int iv) {
 // collective call, include/omg.h), checked under OMG_CHECK_COLLECTIVE.
 static void deep_before(omg_ctx* c, Level* L, int colour) {
   if (!L->deep) return;
+  materialize_rhs(c, L);   // (its rhs round copies rhs as stored; a split level never has shifts pending)
   const LevelView V = L->view();
   if (c->check_collective && (allreduce(c, L->prox_rhs_ok ? 1.0 : 0.0, true) > 0.5) != L->prox_rhs_ok)
     throw OmgError("deep halo: the rhs refill decision differs across ranks (an rhs write was not collective)");
@@ -226,6 +227,7 @@ bool smooth_boxes(omg_ctx* c, int lvl, int n_cycle, int first_substep, int skip_
                       !L->has_rb && gs_tiled(L->nc, c->op, L->has_rb) && !(L->d_b3 && L->b3_phys);
   if (L->shift_pending && !absorb) materialize_level(c, L);
   if (c->smoother != OMG_SMOOTHER_GSRB) {
+    materialize_rhs(c, L);   // (the lexicographic sweeps read rhs as stored)
     // the register-ring kernel reads rhs from its ring-order copy, rebuilt
     // here when a write since the last build dropped it (update_coarse for
     // the levels below the top, every entry point that may change rhs)
@@ -313,10 +315,12 @@ bool smooth_boxes(omg_ctx* c, int lvl, int n_cycle, int first_substep, int skip_
     if (four && (n_sub - n + 1) % 4 == 0 && b3 && (!ph || c->block4_phys)) {
       double* other = L->d_phi == L->d_data ? L->d_phi_buf : L->d_data;
       deep_before(c, L, 1 - e);
+      if (ph) materialize_rhs(c, L);   // (the form with physical faces takes no list)
       {
+        // (the level's pending rhs shifts are subtracted at the loads)
         Prof p(c, "smoother_gsrb4", 2.0 * L->n * L->nc * L->nc * L->nc, lvl);
         launch_gsrb4(L->view(), other, L->d_b3, L->n_b3, c->op, c->lambda, e, shift, c->stream, nullptr, nullptr,
-                     ph);
+                     ph, true, rhs_shifts(c, L));
       }
       L->d_phi = other;
       if (L->gc_deferred) L->phi_gc_ok = true, L->gc_deferred = false;   // (it wrote every ghost face)
@@ -332,6 +336,7 @@ bool smooth_boxes(omg_ctx* c, int lvl, int n_cycle, int first_substep, int skip_
       // (a split level: both colours, its remote faces' ghosts arrive whole)
       const bool push1 = L->deep || !(skip_last == 1 && n + 2 == n_sub && e == 1);
       const bool res = want_res && n + 2 == n_sub && push1;
+      materialize_rhs(c, L);   // (k_gsrb3 reads rhs as stored)
       deep_before(c, L, 1 - e);
       {
         Prof p(c, res ? "smoother_gsrb3r" : "smoother_gsrb3", 1.5 * L->n * L->nc * L->nc * L->nc, lvl);
@@ -348,8 +353,10 @@ bool smooth_boxes(omg_ctx* c, int lvl, int n_cycle, int first_substep, int skip_
       n += 2;
       continue;
     }
-    // (the one-substep kernels read the ghosts: a deferred fill runs first)
+    // (the one-substep kernels read the ghosts: a deferred fill runs first;
+    // and rhs as stored)
     if (L->gc_deferred) fill_gc_lvl(c, lvl, 1);
+    materialize_rhs(c, L);
     if (L->n_bnd && L->n_int && !odd && gs_tiled(L->nc, c->op, L->has_rb)) {
       // boxes with faces on other GPUs first; their halo travels on the comm
       // stream while the interior boxes run (the substep reads only its own
@@ -405,9 +412,11 @@ static bool tiled_level(omg_ctx* c, const Level* L) {
 void residual_lvl(omg_ctx* c, int lvl, unsigned long long* maxbits) {
   Level* L = level_ptr(c, lvl);
   if (!L || L->n == 0) return;
+  if (!tiled_level(c, L)) materialize_rhs(c, L);
   Prof p(c, "residual", (double)L->n * L->nc * L->nc * L->nc, lvl);
   if (tiled_level(c, L))
-    launch_resid_restrict(L->sweep_view(), empty_view(), c->op, c->lambda, maxbits, 0, nullptr, nullptr, c->stream);
+    launch_resid_restrict(L->sweep_view(), empty_view(), c->op, c->lambda, maxbits, 0, nullptr, nullptr, c->stream,
+                          nullptr, 0, rhs_shifts(c, L));
   else
     launch_residual(L->view(), c->op, c->lambda, maxbits, c->stream);
 }
@@ -524,7 +533,11 @@ void update_coarse(omg_ctx* c, int lvl, bool fused, bool tail_crhs) {
     // the fill below every ghost face: a pending shift there is dead
     if (Cl->all_parents) Cl->shift_pending = false;
     else materialize_level(c, Cl);
+    materialize_rhs(c, Cl);
   }
+  // (k_resid_restrict takes the level's pending rhs shifts; the fused forms
+  // and the untiled residual read rhs as stored)
+  if (F && (fused || !tiled_level(c, F))) materialize_rhs(c, F);
   if (F && F->n && tiled_level(c, F)) {
     // The stored refinement-boundary coarse parts of lvl (d_rbgv) were formed
     // from lvl-1 as it stands until the restriction below writes it, which is
@@ -574,7 +587,7 @@ void update_coarse(omg_ctx* c, int lvl, bool fused, bool tail_crhs) {
       {
         Prof p(c, "resid_restrict", (double)F->n_bnd * F->nc * F->nc * F->nc, lvl);
         launch_resid_restrict(F->sweep_view(), view_of(c, lvl - 1), c->op, c->lambda, nullptr, 1, F->d_parent_local,
-                              F->d_dix, c->stream, F->d_bnd, F->n_bnd);
+                              F->d_dix, c->stream, F->d_bnd, F->n_bnd, rhs_shifts(c, F));
       }
     } else if (fused) {
       Prof p(c, "smooth_resid", (double)F->n * F->nc * F->nc * F->nc, lvl);
@@ -588,18 +601,18 @@ void update_coarse(omg_ctx* c, int lvl, bool fused, bool tail_crhs) {
       {
         Prof p(c, "resid_restrict", (double)F->n_int * F->nc * F->nc * F->nc, lvl);
         launch_resid_restrict(F->sweep_view(), view_of(c, lvl - 1), c->op, c->lambda, nullptr, 1, F->d_parent_local,
-                              F->d_dix, c->stream, F->d_int, F->n_int);
+                              F->d_dix, c->stream, F->d_int, F->n_int, rhs_shifts(c, F));
       }
       faces_join(c, F);
       {
         Prof p(c, "resid_restrict", (double)F->n_bnd * F->nc * F->nc * F->nc, lvl);
         launch_resid_restrict(F->sweep_view(), view_of(c, lvl - 1), c->op, c->lambda, nullptr, 1, F->d_parent_local,
-                              F->d_dix, c->stream, F->d_bnd, F->n_bnd);
+                              F->d_dix, c->stream, F->d_bnd, F->n_bnd, rhs_shifts(c, F));
       }
     } else {
       Prof p(c, "resid_restrict", (double)F->n * F->nc * F->nc * F->nc, lvl);
       launch_resid_restrict(F->sweep_view(), view_of(c, lvl - 1), c->op, c->lambda, nullptr, 1, F->d_parent_local,
-                            F->d_dix, c->stream);
+                            F->d_dix, c->stream, nullptr, 0, rhs_shifts(c, F));
     }
     restrict_remote(c, 1, lvl);
     restrict_remote(c, 4, lvl);
@@ -664,6 +677,7 @@ static bool prolong_smooth(omg_ctx* c, int lvl) {
       (c->n_ranks > 1 && (F->prol.n_send || F->prol.n_recv)))
     return false;
   if (F->shift_pending) materialize_level(c, F);
+  materialize_rhs(c, F);   // (k_prolong_smooth and the one-substep kernel read rhs as stored)
   rb_stale_above(c, lvl + 1);
   const bool split = F->has_remote;
   {
@@ -742,9 +756,10 @@ static int correct_block3(omg_ctx* c, int l, bool res_ready, bool defer_gc = fal
                !c->no_defer_gc;
     Prof p(c, "smoother_gsrb4p", 2.0 * F->n * F->nc * F->nc * F->nc, l);
     launch_gsrb4(F->view(), other, F->d_b3, F->n_b3, c->op, c->lambda, 1, nullptr, c->stream, &cv, F->d_b3c,
-                 nullptr, !deferred);
+                 nullptr, !deferred, rhs_shifts(c, F));
     done = 4;
   } else {
+    materialize_rhs(c, F);   // (k_gsrb3 reads rhs as stored)
     Prof p(c, "smoother_gsrb3p", 1.5 * F->n * F->nc * F->nc * F->nc, l);
     launch_gsrb3(F->view(), other, F->d_b3, F->n_b3, c->op, c->lambda, 1, nullptr, c->stream, true, &cv, F->d_b3c,
                  res_ready ? 2 : 1);
@@ -865,6 +880,7 @@ static void run_tail(omg_ctx* c, int top, bool top_crhs) {
       if (L->all_parents && l < top) L->shift_pending = false;   // overwritten by the restriction
       else materialize_level(c, L);
     }
+    materialize_rhs(c, L);   // (the tail reads and writes rhs as stored)
     L->rhs_lex_ok = L->prox_rhs_ok = false;   // the tail writes the rhs of the levels below its top
     TailLevel& T = A.lv[l - c->lowest];
     T.L = L->view();
@@ -949,6 +965,14 @@ double fas_vcycle(omg_ctx* c, int highest_lvl, bool want_max_res, bool standalon
       }
     }
   }
+  // rhs shifts a stand-alone cycle left pending stay so through the next one
+  // (subtract_mean adds this cycle's); any other cycle writes them out first
+  if (!full) materialize_rhs_all(c);
+  struct FullCycle {   // materialize_rhs notes the readers that ran without the list
+    omg_ctx* c;
+    ~FullCycle() { c->in_full_cycle = false; }
+  } full_cycle{c};
+  c->in_full_cycle = full;
   if (c->subtract_mean && !has_highest) subtract_mean(c, 2, 0, full ? kInCycle : kPlain);
   if (standalone) {
     // the fill is idempotent: skip it when the ghosts already equal its result.
@@ -1068,6 +1092,7 @@ double fas_vcycle(omg_ctx* c, int highest_lvl, bool want_max_res, bool standalon
 
 // mg_fas_fmg (m_multigrid.f90:84-147)
 double fas_fmg(omg_ctx* c, bool have_guess, bool want_max_res) {
+  materialize_rhs_all(c);
   if (have_guess) {
     materialize_phi(c);
   } else {
@@ -1217,6 +1242,7 @@ void set_operator(omg_ctx* c, int op, double lambda) {
     throw OmgError("vlaplacian/vhelmholtz_set_methods: mg%n_extra_vars == 0");
   if (op == OMG_VLAPLACIAN) lambda = 0.0;
   const bool changed = c->op != op;
+  if (changed) rhs_pend_retry(c);
   c->op = op;
   c->lambda = lambda;
   if (changed && !c->capturing) ensure_rhs_lex(c);

@@ -142,6 +142,44 @@ __device__ __forceinline__ void launch_max(unsigned long long* maxbits, double m
   }
 }
 
+// A level's pending rhs mean shifts (RhsShifts) at a load: the means are
+// wave-uniform (scalar loads, held in SGPRs) and every loaded rhs value
+// becomes ((v - s0) - s1) - ..., the bits the stored value would have had
+// (no contraction, no reassociation: the library builds without fast-math).
+struct RhsSub {
+  double s[kRhsPendMax + 1];
+  int n;
+  __device__ __forceinline__ RhsSub(const double* __restrict__ p, int n_) : n(n_) {
+#pragma unroll
+    for (int i = 0; i <= kRhsPendMax; i++) s[i] = i < n ? p[i] : 0.0;
+  }
+  __device__ __forceinline__ void operator()(double& a, double& b) const {
+#pragma unroll
+    for (int i = 0; i <= kRhsPendMax; i++)
+      if (i < n) {
+        a = a - s[i];
+        b = b - s[i];
+      }
+  }
+};
+
+// (the count known at compile time: exactly N subtractions, no branch)
+template <int N>
+struct RhsSubN {
+  double s[N > 0 ? N : 1];
+  __device__ __forceinline__ explicit RhsSubN(const double* __restrict__ p) {
+#pragma unroll
+    for (int i = 0; i < N; i++) s[i] = p[i];
+  }
+  __device__ __forceinline__ void operator()(double& a, double& b) const {
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+      a = a - s[i];
+      b = b - s[i];
+    }
+  }
+};
+
 template <int OP>
 struct OpCoef {
   double ix, iy, iz, fac, lambda;

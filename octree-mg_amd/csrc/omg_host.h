@@ -280,6 +280,10 @@ double get_sum(omg_ctx* c, int iv);
 void phi_mean_ready(omg_ctx* c);
 void materialize_level(omg_ctx* c, Level* L);
 void materialize_phi(omg_ctx* c);
+RhsShifts rhs_shifts(omg_ctx* c, const Level* L);
+void materialize_rhs(omg_ctx* c, Level* L);
+void materialize_rhs_all(omg_ctx* c);
+void rhs_pend_retry(omg_ctx* c);   // the smoothing counts, the smoother or the operator changed
 void drop_rhs_lex(omg_ctx* c);
 void enter(omg_ctx* c, bool writes = true);
 enum { kPlain = 0, kInCycle = 1 };

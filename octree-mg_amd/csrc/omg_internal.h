@@ -37,6 +37,23 @@ constexpr int kMaxVars = 16;
 // boxes: 102 against 126)
 constexpr int kB3MinBoxes = 4096;
 
+// Pending rhs mean shifts (omg_mean.cpp): a stand-alone periodic cycle's
+// rhs -= mean stays unwritten on a level for up to this many cycles in a row;
+// the passes that read rhs subtract the listed means while loading, and the
+// cycle after writes them all out.  (1 / 3 / 4 measured, DESIGN.md.)
+#ifdef OMG_RHS_PEND_MAX   // (another depth for A/B timing)
+constexpr int kRhsPendMax = OMG_RHS_PEND_MAX;
+#else
+constexpr int kRhsPendMax = 4;
+#endif
+
+// The list a kernel takes: it subtracts s[0..n) in this order from every rhs
+// value it loads (n = 0: rhs as stored).
+struct RhsShifts {
+  const double* s = nullptr;
+  int n = 0;
+};
+
 // Physical boundary condition of one variable (mg%bc(:, iv)).
 struct BCVar {
   int type[6];
@@ -168,6 +185,14 @@ struct Level {
   bool all_parents = false;      // every box of this rank at this level is a parent
   bool prolong_smooth_ok = false;  // k_prolong_smooth can serve this level (see build_plan)
   bool shift_pending = false;    // phi -= mean still to apply (see subtract_mean)
+  // rhs -= mean still to apply: the last rhs_pend entries of the context's
+  // list (omg_ctx::d_rhs_pend, entries rhs_n - rhs_pend .. rhs_n - 1), in
+  // that order (materialize_rhs)
+  int rhs_pend = 0;
+  // a reader that takes no list had to write the shifts out during a
+  // stand-alone cycle: the level's cycles subtract at once (today's pass)
+  // until the smoothing counts, the smoother or the operator change
+  bool rhs_pend_off = false;
   int8_t* d_nbk = nullptr;
   int* d_nba = nullptr;
   int* d_sendpos = nullptr;
@@ -358,6 +383,13 @@ struct omg_ctx {
   std::map<int, std::vector<int>> h_face_type_lvl[omg::kMaxVars];
   // scalars
   double* d_red = nullptr;             // device reductions (get_sum / subtract_mean)
+  // the rhs means of the last rhs_n stand-alone cycles, in order (k_mean
+  // writes each one here; they never visit the host), kRhsPendMax + 1 doubles:
+  // the cycle that writes the list out appends its own mean first
+  double* d_rhs_pend = nullptr;
+  int rhs_n = 0;
+  bool in_full_cycle = false;          // inside a stand-alone cycle over the whole tree (fas_vcycle)
+  bool no_rhs_pend = false;            // OMG_NO_RHS_PEND: every cycle writes rhs - mean at once
   hipStream_t stream2 = nullptr;       // side stream (rhs sum chain)
   hipStream_t stream_comm = nullptr;   // halo exchange overlapped with interior boxes (highest priority)
   int comm_priority = 0;               // its priority (hipDeviceGetStreamPriorityRange's greatest)

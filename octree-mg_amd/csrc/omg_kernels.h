@@ -77,7 +77,8 @@ struct B3Phys {
 // level's ghosts deferred: Level::gc_deferred)
 void launch_gsrb4(const LevelView& L, double* dst, const int* cols, int n_cols, int op, double lambda, int e,
                   const double* shift, hipStream_t st, const LevelView* coarse = nullptr,
-                  const int* ccols = nullptr, const B3Phys* phys = nullptr, bool push = true);
+                  const int* ccols = nullptr, const B3Phys* phys = nullptr, bool push = true,
+                  RhsShifts rs = RhsShifts());
 // push1 false: the ghost faces get the colour-e cells only (the colour-(1-e)
 // halves are left stale: only for a pass that k_smooth_resid follows, which
 // reads colour e's and forms colour 1-e's itself)
@@ -249,7 +250,8 @@ bool launch_smooth_resid(const LevelView& F, const LevelView& C, int op, double 
                          int n_list, const GcBC& bc, bool has_rb, bool has_phys, const double* rbgv = nullptr);
 void launch_resid_restrict(const LevelView& F, const LevelView& C, int op, double lambda,
                            unsigned long long* maxbits, int restrict_on, const int* parent_local,
-                           const int* dixp, hipStream_t st, const int* list = nullptr, int n_list = 0);
+                           const int* dixp, hipStream_t st, const int* list = nullptr, int n_list = 0,
+                           RhsShifts rs = RhsShifts());
 // sub: form the parent's res = phi - old on the fly (and store it) instead of
 // reading it (correct_children's parent loop fused in); skip1: a colour-1
 // red-black substep follows, so all-local boxes correct and push colour 0 only
@@ -278,9 +280,12 @@ void launch_fill_crhs(const LevelView& C, int op, double lambda, const GcBC& bc,
                       hipStream_t st);
 bool launch_coarse_rhs_tile(const LevelView& C, int op, double lambda, const int* parents, int n_par,
                             hipStream_t st);
-void launch_box_sums(const LevelView& L, int iv, const int* leaves, int n, double* out, hipStream_t st);
+// rs: the box sums of the values less the listed shifts (nothing is stored)
+void launch_box_sums(const LevelView& L, int iv, const int* leaves, int n, double* out, hipStream_t st,
+                     RhsShifts rs = RhsShifts());
 bool subtract_sums_nc(int nc);
-void launch_subtract_sums(const LevelView& L, int iv, const int* leaves, int n, const double* mean, double* out,
+// every value less rs.s[0 .. rs.n) in that order, stored, and its box sums
+void launch_subtract_sums(const LevelView& L, int iv, const int* leaves, int n, RhsShifts rs, double* out,
                           hipStream_t st);
 void launch_mean(const double* all, int n, double volume, double* mean, hipStream_t st);
 // init: start from +0.0 instead of *acc

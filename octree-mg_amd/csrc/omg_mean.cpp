@@ -1,6 +1,7 @@
 // omg_mean.cpp — get_sum / subtract_mean for periodic problems: the leaf
-// sums and the mean on the device, the pending phi shift a stand-alone cycle
-// leaves behind, and what every entry point does about both (enter).
+// sums and the mean on the device, the pending phi shift and the pending rhs
+// shifts a stand-alone cycle leaves behind, and what every entry point does
+// about them (enter).
 #include <algorithm>
 
 #include "omg_host.h"
@@ -31,7 +32,9 @@ static void leaf_box_sums(omg_ctx* c, int iv, int ch, hipStream_t st) {
     Level* L = level_ptr(c, l);
     if (!L || L->leaves.empty()) continue;
     Prof p(c, "box_sums", (double)L->leaves.size() * L->nc * L->nc * L->nc, l, st);
-    launch_box_sums(L->sweep_view(), iv, L->d_leaves, (int)L->leaves.size(), leaf_scratch(L, ch), st);
+    // (rhs: the sums of the values its pending shifts leave)
+    launch_box_sums(L->sweep_view(), iv, L->d_leaves, (int)L->leaves.size(), leaf_scratch(L, ch), st,
+                    iv == 2 ? rhs_shifts(c, L) : RhsShifts());
   }
 }
 
@@ -62,7 +65,7 @@ static double subtract_volume(omg_ctx* c) {
 
 // MPI_Allreduce(acc) / volume into red_mean(ch), without leaving the stream
 // (RCCL all-gather + k_mean); the loopback transport gathers on the host.
-static void mean_device(omg_ctx* c, int ch) {
+static void mean_device(omg_ctx* c, int ch, double* mean) {
   const int n = c->n_ranks;
   if (n > 64) throw OmgError("subtract_mean: more than 64 ranks");
   double* all = red_all(c, ch);
@@ -77,7 +80,7 @@ static void mean_device(omg_ctx* c, int ch) {
   } else {
     NCCLCHK(ncclAllGather(red_acc(c, ch), all, 1, ncclDouble, (ncclComm_t)c->nccl, c->stream));
   }
-  launch_mean(all, n, subtract_volume(c), red_mean(c, ch), c->stream);
+  launch_mean(all, n, subtract_volume(c), mean, c->stream);
 }
 
 // get_sum + MPI_Allreduce(sum) as one value on the host (omg_get_sum)
@@ -94,7 +97,7 @@ void phi_mean_ready(omg_ctx* c) {
   if (!c->phi_mean_on_side) return;
   c->phi_mean_on_side = false;
   HIPCHK(hipStreamWaitEvent(c->stream, c->ev_phi, 0));
-  if (c->n_ranks > 1) mean_device(c, kChPhi);
+  if (c->n_ranks > 1) mean_device(c, kChPhi, red_mean(c, kChPhi));
 }
 
 // A pending phi -= mean (left by a standalone V-cycle, see subtract_mean) is
@@ -114,6 +117,52 @@ void materialize_phi(omg_ctx* c) {
   for (auto& kv : c->levels) materialize_level(c, &kv.second);
   c->phi_shift_pending = false;
 }
+
+// Pending rhs shifts.  mg_fas_vcycle begins every periodic cycle with
+// rhs <- rhs - mean(rhs) (m_multigrid.f90:245-276).  A stand-alone cycle
+// leaves that pending on the levels whose passes take the list (k_gsrb4,
+// k_resid_restrict, the box sums): the mean joins the context's list
+// (d_rhs_pend, written by k_mean on the stream), the level counts it
+// (Level::rhs_pend), and every pass subtracts the level's part of the list
+// from the rhs values it loads, in order: ((rhs - M1) - M2) - ..., the bits
+// the stored value would have had.  The cycle that finds the list full writes
+// it out with its own mean (the storing form of the sums kernel).  Anything
+// else that reads or writes rhs writes the shifts out first (materialize_rhs:
+// enter() for the entry points, the other readers inside a cycle themselves).
+// One rank only: a split level's deep-halo proxies hold rhs as well and every
+// rank would have to decide alike; multi-rank runs subtract at once, as before.
+RhsShifts rhs_shifts(omg_ctx* c, const Level* L) {
+  RhsShifts r;
+  r.s = c->d_rhs_pend + (c->rhs_n - L->rhs_pend);
+  r.n = L->rhs_pend;
+  return r;
+}
+// The stored values catch up with the list; the box sums in the level's
+// scratch and the chained sum are those of the same values and stay valid.
+void materialize_rhs(omg_ctx* c, Level* L) {
+  if (!L->rhs_pend) return;
+  // inside a stand-alone cycle: a reader that takes no list ran on this level
+  if (c->in_full_cycle) L->rhs_pend_off = true;
+  {
+    Prof p(c, "subtract_rhs", (double)L->n * L->nc * L->nc * L->nc, L->lvl);
+    launch_subtract_sums(L->sweep_view(), 2, L->d_leaves, L->n, rhs_shifts(c, L), nullptr, c->stream);
+  }
+  L->rhs_pend = 0;
+  L->rhs_lex_ok = L->prox_rhs_ok = false;
+}
+void materialize_rhs_all(omg_ctx* c) {
+  for (auto& kv : c->levels) materialize_rhs(c, &kv.second);
+}
+void rhs_pend_retry(omg_ctx* c) {
+  for (auto& kv : c->levels) kv.second.rhs_pend_off = false;
+}
+// whether a cycle may leave the level's rhs - mean pending: its passes are
+// the block passes that take the list
+static bool rhs_pend_ok(omg_ctx* c, const Level* L) {
+  return c->n_ranks == 1 && c->smoother == OMG_SMOOTHER_GSRB && !c->no_rhs_pend && L->d_b3 && !L->b3_phys &&
+         !L->rhs_pend_off;
+}
+
 // the ring-order rhs copies: every write of a level's rhs drops its copy
 void drop_rhs_lex(omg_ctx* c) {
   for (auto& kv : c->levels) kv.second.rhs_lex_ok = kv.second.prox_rhs_ok = false;
@@ -125,6 +174,7 @@ static void drop_rhs_cache(omg_ctx* c) {
 // entry points other than the cycles: apply pending phi work first; `writes`
 // = the call may change rhs (the cached rhs sum is dropped)
 void enter(omg_ctx* c, bool writes) {
+  materialize_rhs_all(c);
   materialize_phi(c);
   for (auto& kv : c->levels)
     if (kv.second.gc_deferred) fill_gc_lvl(c, kv.first, 1);
@@ -146,6 +196,7 @@ void subtract_mean(omg_ctx* c, int iv, int ghosts, int mode) {
     for (auto& kv : c->levels)
       if (!ghosts || kv.second.any_phys || kv.second.any_rb) kv.second.phi_gc_ok = false;
   }
+  if (iv == 2 && (ghosts || mode != kInCycle)) materialize_rhs_all(c);
   if (iv == 2 && !ghosts) {
     // rhs: the sums may already be running on the side stream (see below)
     if (c->rhs_cache_valid) {
@@ -160,7 +211,15 @@ void subtract_mean(omg_ctx* c, int iv, int ghosts, int mode) {
     for (auto& kv : c->levels)
       if (kv.second.prox_rhs_ok) prox_kept.push_back(kv.first);
     drop_rhs_lex(c);
-    mean_device(c, kChRhs);
+    // the mean goes to the end of the list of pending shifts (empty again
+    // once no level has any pending); a full list is written out by this
+    // cycle, its own mean included
+    bool any_pend = false;
+    for (auto& kv : c->levels) any_pend = any_pend || kv.second.rhs_pend > 0;
+    if (!any_pend) c->rhs_n = 0;
+    const bool list_full = c->rhs_n >= kRhsPendMax;
+    double* mean = c->d_rhs_pend + c->rhs_n;
+    mean_device(c, kChRhs, mean);
     bool all_fused = true;
     for (int l = c->lowest; l <= c->highest; l++) {
       Level* L = level_ptr(c, l);
@@ -171,17 +230,32 @@ void subtract_mean(omg_ctx* c, int iv, int ghosts, int mode) {
         P.data += (long long)L->n * L->stride;
         P.phi += (long long)L->n * L->stride;
         P.n = L->n_prox;
-        launch_subtract(P, 2, red_mean(c, kChRhs), 0, c->stream);
+        launch_subtract(P, 2, mean, 0, c->stream);
         L->prox_rhs_ok = true;
       }
-      Prof p(c, "subtract_rhs", (double)L->n * L->nc * L->nc * L->nc, l);
-      if (l >= 1 && (int)L->leaves.size() == L->n && subtract_sums_nc(L->nc))
-        launch_subtract_sums(L->sweep_view(), 2, L->d_leaves, L->n, red_mean(c, kChRhs), L->d_scratch_rhs, c->stream);
-      else {
-        launch_subtract(L->view(), 2, red_mean(c, kChRhs), 0, c->stream);
+      const double cells = (double)L->n * L->nc * L->nc * L->nc;
+      if (l >= 1 && (int)L->leaves.size() == L->n && subtract_sums_nc(L->nc)) {
+        // the level's pending shifts and the new mean; either form leaves the
+        // box sums of the shifted values for the next get_sum
+        RhsShifts rs = rhs_shifts(c, L);
+        rs.n++;
+        if (mode == kInCycle && !list_full && rhs_pend_ok(c, L)) {
+          Prof p(c, "box_sums", cells, l);
+          launch_box_sums(L->sweep_view(), 2, L->d_leaves, L->n, L->d_scratch_rhs, c->stream, rs);
+          L->rhs_pend++;
+        } else {
+          Prof p(c, "subtract_rhs", cells, l);
+          launch_subtract_sums(L->sweep_view(), 2, L->d_leaves, L->n, rs, L->d_scratch_rhs, c->stream);
+          L->rhs_pend = 0;
+        }
+      } else {
+        materialize_rhs(c, L);   // (never pending here: such a level's cycles subtract at once)
+        Prof p(c, "subtract_rhs", cells, l);
+        launch_subtract(L->view(), 2, mean, 0, c->stream);
         if (l >= 1 && !L->leaves.empty()) all_fused = false;
       }
     }
+    c->rhs_n = list_full ? 0 : c->rhs_n + 1;
     if (all_fused) {
       // the next get_sum(rhs): its leaf sums were produced by the fused
       // kernels; its sequential chain runs now on the side stream
@@ -211,7 +285,7 @@ void subtract_mean(omg_ctx* c, int iv, int ghosts, int mode) {
     return;
   }
   leaf_sum_device(c, iv, ch);
-  mean_device(c, ch);
+  mean_device(c, ch, red_mean(c, ch));
   for (int l = c->lowest; l <= c->highest; l++) {
     Level* L = level_ptr(c, l);
     // (phi of every level changes: the refinement-boundary coarse parts the

@@ -10,6 +10,9 @@
 //    recomputed.  Nothing reads fine ghosts during the launch: race-free.
 //  k_box_sums3 / k_seq_sum3: get_sum (:278-294) in the reference's exact
 //    sequential order, with wide loads and the products off the add chain.
+#include <stdexcept>
+#include <string>
+
 #include "omg_face.h"
 #include "omg_gsrb.h"
 #include "omg_kernels.h"
@@ -33,7 +36,8 @@ __device__ __forceinline__ void resid_restrict_core(const LevelView& F, const Le
 template <int NC, int OP, int BS>
 __device__ __forceinline__ void resid_restrict_box(const LevelView& F, const LevelView& Cv, double lambda,
                                                    unsigned long long* maxbits, int restrict_on,
-                                                   const int* parent_local, const int* dixp, int b, double* sb) {
+                                                   const int* parent_local, const int* dixp, int b, double* sb,
+                                                   const double* __restrict__ rsh = nullptr, int n_rsh = 0) {
   using TL = Tl<NC>;
   constexpr int NST = TL::NST, HV = TL::HV, NR = (HV + BS - 1) / BS;
   const int tid = threadIdx.x;
@@ -46,6 +50,18 @@ __device__ __forceinline__ void resid_restrict_box(const LevelView& F, const Lev
   for (int r = 0; r < NR; r++) {
     const int q2 = tid + BS * r;
     if (q2 < HV) fr[r] = ld_nt(f + 2 * q2);
+  }
+  // (the level's pending rhs mean shifts, subtracted at the load)
+  if (n_rsh) {
+    const RhsSub rsub(rsh, n_rsh);
+#pragma unroll
+    for (int r = 0; r < NR; r++)
+      if (tid + BS * r < HV) {
+        double a = fr[r].x, b2 = fr[r].y;
+        rsub(a, b2);
+        fr[r].x = a;
+        fr[r].y = b2;
+      }
   }
   __syncthreads();
   resid_restrict_core<NC, OP, BS>(F, Cv, lambda, maxbits, restrict_on, parent_local, dixp, b, sb, fr);
@@ -134,10 +150,12 @@ template <int NC, int OP, int BS>
 __global__ void __launch_bounds__(BS) k_resid_restrict(LevelView F, LevelView Cv, double lambda,
                                                        unsigned long long* maxbits, int restrict_on,
                                                        const int* parent_local, const int* dixp,
-                                                       const int* list) {
+                                                       const int* list, const double* __restrict__ rsh,
+                                                       int n_rsh) {
   __shared__ double sb[Tl<NC>::NST];
   const int q = xcd_box(blockIdx.x, gridDim.x, F.rev);
-  resid_restrict_box<NC, OP, BS>(F, Cv, lambda, maxbits, restrict_on, parent_local, dixp, list ? list[q] : q, sb);
+  resid_restrict_box<NC, OP, BS>(F, Cv, lambda, maxbits, restrict_on, parent_local, dixp, list ? list[q] : q, sb,
+                                 rsh, n_rsh);
 }
 
 // Tile offset of the cell at layer v along axis d and tangential (a, c)
@@ -760,6 +778,9 @@ void launch_prolong_smooth(const LevelView& C, const LevelView& F, int op, doubl
 // SUB: subtract_mean fused in front (m_multigrid.f90:268-272, no ghosts): every
 // value is replaced by v - mean in HBM and the box sums are those of the new
 // values (what the next get_sum of this variable will need).
+// shifts: the sums are those of ((v - s0) - s1) - ... (a level's pending rhs
+// mean shifts with the cycle's new mean last); SUB stores those values, the
+// plain form only sums them.
 // NT: non-temporal streams (the level is read once per pass)
 template <bool NT>
 __device__ __forceinline__ double2 sums_ld(const double* p) {
@@ -777,10 +798,11 @@ __device__ __forceinline__ void sums_st(double* p, double2 v) {
     *reinterpret_cast<double2*>(p) = v;
 }
 
-template <int NC, bool SUB, int LPW = kSumsLPW>
+// SH: the launch has shifts (false: the plain sums, phi's pass, hold no trace of them)
+template <int NC, bool SUB, bool SH = SUB, int LPW = kSumsLPW>
 __global__ void __launch_bounds__(64) k_box_sums3(LevelView L, int iv, const int* __restrict__ leaves,
                                                   int n_leaves, double* __restrict__ out,
-                                                  const double* __restrict__ mean) {
+                                                  const double* __restrict__ shifts, int n_sh) {
   constexpr int H = NC / 2, R = kSumsR < NC ? kSumsR : NC, SEG = R * H;   // doubles of one colour in a chunk
   constexpr bool NTL = SUB ? kSubNTLd : kSumsNT;
   constexpr int CH2 = SEG;                        // double2 per box per chunk (2 colours)
@@ -801,7 +823,8 @@ __global__ void __launch_bounds__(64) k_box_sums3(LevelView L, int iv, const int
     src[r] = boxp(L, iv, leaves[q]) + seg * hv + 2 * off;
     dst[r] = bb * P + seg * SEG + 2 * off;
   }
-  const double m = SUB ? *mean : 0.0;
+  static_assert(SH || !SUB, "k_box_sums3: the storing form subtracts");
+  const RhsSub rsub(shifts, SH ? n_sh : 0);
   // two chunks in flight (vmcnt counts loads and stores together, in issue
   // order: with one chunk of lookahead every chunk's loads also waited for the
   // previous chunk's stores)
@@ -818,11 +841,8 @@ __global__ void __launch_bounds__(64) k_box_sums3(LevelView L, int iv, const int
     const int rc = chunk_off(c);
 #pragma unroll
     for (int r = 0; r < PER; r++) {
-      if (SUB) {
-        v[r].x = v[r].x - m;
-        v[r].y = v[r].y - m;
-        if (own[r]) sums_st<kSubNTSt>(src[r] + rc, v[r]);
-      }
+      if (SH) rsub(v[r].x, v[r].y);
+      if (SUB && own[r]) sums_st<kSubNTSt>(src[r] + rc, v[r]);
       lds[dst[r]] = v[r].x;
       lds[dst[r] + 1] = v[r].y;
     }
@@ -852,7 +872,8 @@ __global__ void __launch_bounds__(64) k_box_sums3(LevelView L, int iv, const int
     process(va, c);
     process(vb, c + 1);
   }
-  if (lane < LPW && b0 + lane < n_leaves) out[b0 + lane] = acc;
+  // (out null: the sums are known already, materialize_rhs)
+  if (out && lane < LPW && b0 + lane < n_leaves) out[b0 + lane] = acc;
 }
 
 // generic box size: one lane per leaf straight from HBM
@@ -1034,12 +1055,15 @@ bool tiled_nc(int nc) { return nc == 16 || nc == 8 || nc == 4 || nc == 2; }
 
 void launch_resid_restrict(const LevelView& F, const LevelView& C, int op, double lambda,
                            unsigned long long* maxbits, int restrict_on, const int* parent_local,
-                           const int* dixp, hipStream_t st, const int* list, int n_list) {
+                           const int* dixp, hipStream_t st, const int* list, int n_list, RhsShifts rs) {
   const int n = list ? n_list : F.n;
   if (n == 0) return;
+  if (rs.n < 0 || rs.n > kRhsPendMax || (rs.n && !rs.s))
+    throw std::runtime_error("launch_resid_restrict: at most kRhsPendMax pending rhs shifts");
   const dim3 g(n);
-#define OMG_RR_OP(NC, BS, OPV) \
-  k_resid_restrict<NC, OPV, BS><<<g, dim3(BS), 0, st>>>(F, C, lambda, maxbits, restrict_on, parent_local, dixp, list);
+#define OMG_RR_OP(NC, BS, OPV)                                                                                  \
+  k_resid_restrict<NC, OPV, BS><<<g, dim3(BS), 0, st>>>(F, C, lambda, maxbits, restrict_on, parent_local, dixp, \
+                                                        list, rs.s, rs.n);
 #define OMG_RR(NC, BS) OMG_FOR_OP(op, OMG_RR_OP, NC, BS)
   switch (F.nc) {
     case 16: OMG_RR(16, 512) break;
@@ -1273,28 +1297,41 @@ bool launch_coarse_rhs_tile(const LevelView& C, int op, double lambda, const int
   return true;
 }
 
-void launch_box_sums(const LevelView& L, int iv, const int* leaves, int n, double* out, hipStream_t st) {
+static void check_shifts(const RhsShifts& rs, const char* who) {
+  if (rs.n < 0 || rs.n > kRhsPendMax + 1 || (rs.n && !rs.s))
+    throw std::runtime_error(std::string(who) + ": at most kRhsPendMax + 1 shifts");
+}
+
+void launch_box_sums(const LevelView& L, int iv, const int* leaves, int n, double* out, hipStream_t st,
+                     RhsShifts rs) {
   if (n == 0) return;
+  check_shifts(rs, "launch_box_sums");
+  if (rs.n && !subtract_sums_nc(L.nc)) throw std::runtime_error("launch_box_sums: shifts need a 16 / 8 / 4 box");
   const dim3 g((n + kSumsLPW - 1) / kSumsLPW);
   switch (L.nc) {
-    case 16: k_box_sums3<16, false><<<g, 64, 0, st>>>(L, iv, leaves, n, out, nullptr); break;
-    case 8: k_box_sums3<8, false><<<g, 64, 0, st>>>(L, iv, leaves, n, out, nullptr); break;
-    case 4: k_box_sums3<4, false><<<g, 64, 0, st>>>(L, iv, leaves, n, out, nullptr); break;
+#define OMG_BS(NC)                                                                         \
+  if (rs.n) k_box_sums3<NC, false, true><<<g, 64, 0, st>>>(L, iv, leaves, n, out, rs.s, rs.n); \
+  else k_box_sums3<NC, false, false><<<g, 64, 0, st>>>(L, iv, leaves, n, out, nullptr, 0);
+    case 16: OMG_BS(16) break;
+    case 8: OMG_BS(8) break;
+    case 4: OMG_BS(4) break;
+#undef OMG_BS
     default: k_box_sums_any<<<(n + 63) / 64, 64, 0, st>>>(L, iv, leaves, n, out); break;
   }
 }
 
 bool subtract_sums_nc(int nc) { return nc == 16 || nc == 8 || nc == 4; }
 
-void launch_subtract_sums(const LevelView& L, int iv, const int* leaves, int n, const double* mean, double* out,
+void launch_subtract_sums(const LevelView& L, int iv, const int* leaves, int n, RhsShifts rs, double* out,
                           hipStream_t st) {
   if (n == 0) return;
+  check_shifts(rs, "launch_subtract_sums");
   const dim3 g((n + kSumsLPW - 1) / kSumsLPW);
   switch (L.nc) {
-    case 16: k_box_sums3<16, true><<<g, 64, 0, st>>>(L, iv, leaves, n, out, mean); break;
-    case 8: k_box_sums3<8, true><<<g, 64, 0, st>>>(L, iv, leaves, n, out, mean); break;
-    case 4: k_box_sums3<4, true><<<g, 64, 0, st>>>(L, iv, leaves, n, out, mean); break;
-    default: break;
+    case 16: k_box_sums3<16, true><<<g, 64, 0, st>>>(L, iv, leaves, n, out, rs.s, rs.n); break;
+    case 8: k_box_sums3<8, true><<<g, 64, 0, st>>>(L, iv, leaves, n, out, rs.s, rs.n); break;
+    case 4: k_box_sums3<4, true><<<g, 64, 0, st>>>(L, iv, leaves, n, out, rs.s, rs.n); break;
+    default: throw std::runtime_error("launch_subtract_sums: box size must be 16, 8 or 4");
   }
 }
 
