@@ -310,6 +310,7 @@ int omg_ctx_create(omg_ctx** out, int device, int rank, int n_ranks, const void*
     c->block4_phys = env_flag("OMG_BLOCK4_PHYS");
     c->no_defer_gc = env_flag("OMG_NO_DEFER_GC");
     c->no_rhs_pend = env_flag("OMG_NO_RHS_PEND");
+    c->no_res_pend = env_flag("OMG_NO_RES_PEND");
     c->no_fuse_down_bc = env_flag("OMG_NO_FUSE_DOWN_BC");
     c->roctx = env_flag("OMG_ROCTX");
     c->debug = env_flag("OMG_DEBUG");

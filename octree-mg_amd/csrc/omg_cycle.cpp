@@ -121,6 +121,7 @@ void fill_gc_lvl(omg_ctx* c, int lvl, int iv) {
   Level* L = level_ptr(c, lvl);
   if (!L) return;
   if (iv == 1) {
+    res_before_write(c, L, L->d_phi);
     L->phi_gc_ok = true;
     L->gc_deferred = false;
     rb_stale_above(c, lvl);   // (the ghosts it sets are read by lvl+1's interpolation)
@@ -227,6 +228,7 @@ bool smooth_boxes(omg_ctx* c, int lvl, int n_cycle, int first_substep, int skip_
                       !L->has_rb && gs_tiled(L->nc, c->op, L->has_rb) && !(L->d_b3 && L->b3_phys);
   if (L->shift_pending && !absorb) materialize_level(c, L);
   if (c->smoother != OMG_SMOOTHER_GSRB) {
+    if (n_sub >= 1) res_before_write(c, L, L->d_phi);
     materialize_rhs(c, L);   // (the lexicographic sweeps read rhs as stored)
     // the register-ring kernel reads rhs from its ring-order copy, rebuilt
     // here when a write since the last build dropped it (update_coarse for
@@ -314,6 +316,7 @@ bool smooth_boxes(omg_ctx* c, int lvl, int n_cycle, int first_substep, int skip_
     const bool b3 = b3_usable(c, lvl, P3, ph);
     if (four && (n_sub - n + 1) % 4 == 0 && b3 && (!ph || c->block4_phys)) {
       double* other = L->d_phi == L->d_data ? L->d_phi_buf : L->d_data;
+      res_before_write(c, L, other);
       deep_before(c, L, 1 - e);
       if (ph) materialize_rhs(c, L);   // (the form with physical faces takes no list)
       {
@@ -336,6 +339,7 @@ bool smooth_boxes(omg_ctx* c, int lvl, int n_cycle, int first_substep, int skip_
       // (a split level: both colours, its remote faces' ghosts arrive whole)
       const bool push1 = L->deep || !(skip_last == 1 && n + 2 == n_sub && e == 1);
       const bool res = want_res && n + 2 == n_sub && push1;
+      res_before_write(c, L, other);
       materialize_rhs(c, L);   // (k_gsrb3 reads rhs as stored)
       deep_before(c, L, 1 - e);
       {
@@ -356,6 +360,7 @@ bool smooth_boxes(omg_ctx* c, int lvl, int n_cycle, int first_substep, int skip_
     // (the one-substep kernels read the ghosts: a deferred fill runs first;
     // and rhs as stored)
     if (L->gc_deferred) fill_gc_lvl(c, lvl, 1);
+    res_before_write(c, L, L->d_phi);
     materialize_rhs(c, L);
     if (L->n_bnd && L->n_int && !odd && gs_tiled(L->nc, c->op, L->has_rb)) {
       // boxes with faces on other GPUs first; their halo travels on the comm
@@ -409,9 +414,50 @@ static bool tiled_level(omg_ctx* c, const Level* L) {
   return L && tiled_nc(L->nc);
 }
 
+// A pending res (Level::res_pend).  On the top level of a stand-alone cycle
+// over the whole tree nothing reads the res that update_coarse's residual
+// stores: its restriction leaves the same launch from registers and LDS, the
+// up leg reads the coarse level's res, and the next cycle's update_coarse (or
+// this cycle's max residual) overwrites every box.  That launch therefore runs
+// without the store (k_resid_restrict's STORE = false) and the level notes the
+// phi buffer it read.  The level's passes alternate between its two buffers,
+// so that buffer is still whole when the cycle ends, ghost faces included,
+// and rhs reads the same through its shifts, whether stored or listed:
+// the storing form over the same inputs gives the bits the skipped store
+// would have.  Whoever may read res stores it first (enter(), the cycles that
+// do not overwrite it, an operator change), and so does any pass about to
+// write the noted buffer (res_before_write).
+void materialize_res(omg_ctx* c, Level* L) {
+  if (!L->res_pend) return;
+  L->res_pend = false;
+  if (!L->n) return;
+  LevelView V = L->sweep_view();
+  V.phi = L->res_src;
+  Prof p(c, "residual", (double)L->n * L->nc * L->nc * L->nc, L->lvl);
+  launch_resid_restrict(V, empty_view(), c->op, c->lambda, nullptr, 0, nullptr, nullptr, c->stream, nullptr, 0,
+                        rhs_shifts(c, L));
+}
+void materialize_res_all(omg_ctx* c) {
+  for (auto& kv : c->levels) materialize_res(c, &kv.second);
+}
+// before a write of the level's phi buffer buf (interior or ghost faces)
+void res_before_write(omg_ctx* c, Level* L, const double* buf) {
+  if (!L || !L->res_pend || L->res_src != buf) return;
+  // inside a stand-alone cycle: these counts make the level's own passes write
+  // the buffer, every cycle would pay the second launch
+  if (c->in_full_cycle) L->res_pend_off = true;
+  materialize_res(c, L);
+}
+// whether update_coarse's residual on a stand-alone cycle's top level may
+// leave its res unstored
+static bool res_pend_ok(omg_ctx* c, const Level* L) {
+  return c->n_ranks == 1 && !c->capturing && !c->no_res_pend && L->n && tiled_level(c, L) && !L->res_pend_off;
+}
+
 void residual_lvl(omg_ctx* c, int lvl, unsigned long long* maxbits) {
   Level* L = level_ptr(c, lvl);
   if (!L || L->n == 0) return;
+  L->res_pend = false;   // (every box's res is written below)
   if (!tiled_level(c, L)) materialize_rhs(c, L);
   Prof p(c, "residual", (double)L->n * L->nc * L->nc * L->nc, lvl);
   if (tiled_level(c, L))
@@ -460,6 +506,7 @@ static void restrict_remote(omg_ctx* c, int iv, int lvl) {
 void restrict_lvl(omg_ctx* c, int iv, int lvl) {
   if (lvl <= c->lowest) throw OmgError("cannot restrict lvl <= lowest_lvl");
   if (iv == 1) phi_dirty(c, lvl - 1);
+  if (Level* Cl = level_ptr(c, lvl - 1); Cl && iv == 1) res_before_write(c, Cl, Cl->d_phi);
   Level* F = level_ptr(c, lvl);
   restrict_remote(c, iv, lvl);
   if (F && F->n_pairs) {
@@ -476,6 +523,7 @@ void prolong(omg_ctx* c, int lvl, int iv, int iv_to, int add) {
   if (iv_to == 1) phi_dirty(c, lvl + 1);
   Level* F = level_ptr(c, lvl + 1);
   Level* C = level_ptr(c, lvl);
+  if (iv_to == 1) res_before_write(c, F, F->d_phi);
   const LevelView FV = view_of(c, lvl + 1), CV = view_of(c, lvl);
   if (c->n_ranks > 1 && F && C && (F->prol.n_send || F->prol.n_recv)) {
     launch_prolong_pack(CV, FV, iv, F->prol.d_send_items, F->prol.n_send, C->d_sendbuf, c->stream);
@@ -525,10 +573,12 @@ static bool smooth_resid_ok(omg_ctx* c, int lvl) {
 // substep is still to do (smooth_resid_ok), k_smooth_resid runs it
 // with tail_crhs the coarse tail forms lvl-1's ghosts and coarse rhs itself
 // (its top level, TailArgs::top_crhs): only the residual and the restriction here
-void update_coarse(omg_ctx* c, int lvl, bool fused, bool tail_crhs) {
+void update_coarse(omg_ctx* c, int lvl, bool fused, bool tail_crhs, bool res_may_pend) {
   Level* F = level_ptr(c, lvl);
+  if (F) F->res_pend = false;   // (every branch below writes res of every box of lvl, or leaves it pending anew)
   if (Level* Cl = level_ptr(c, lvl - 1)) {
     Cl->rhs_lex_ok = Cl->prox_rhs_ok = false;   // its rhs is rewritten below
+    materialize_res(c, Cl);   // (its phi, rhs and res are rewritten below; never pending in a cycle)
     // restriction overwrites every box of an all-parents level (interior), and
     // the fill below every ghost face: a pending shift there is dead
     if (Cl->all_parents) Cl->shift_pending = false;
@@ -610,9 +660,13 @@ void update_coarse(omg_ctx* c, int lvl, bool fused, bool tail_crhs) {
                               F->d_dix, c->stream, F->d_bnd, F->n_bnd, rhs_shifts(c, F));
       }
     } else {
+      // (a stand-alone cycle's top level: res stays unstored, materialize_res)
+      const bool pend = res_may_pend && res_pend_ok(c, F);
       Prof p(c, "resid_restrict", (double)F->n * F->nc * F->nc * F->nc, lvl);
       launch_resid_restrict(F->sweep_view(), view_of(c, lvl - 1), c->op, c->lambda, nullptr, 1, F->d_parent_local,
-                            F->d_dix, c->stream, nullptr, 0, rhs_shifts(c, F));
+                            F->d_dix, c->stream, nullptr, 0, rhs_shifts(c, F), !pend);
+      F->res_pend = pend;
+      F->res_src = pend ? F->d_phi : nullptr;
     }
     restrict_remote(c, 1, lvl);
     restrict_remote(c, 4, lvl);
@@ -677,6 +731,7 @@ static bool prolong_smooth(omg_ctx* c, int lvl) {
       (c->n_ranks > 1 && (F->prol.n_send || F->prol.n_recv)))
     return false;
   if (F->shift_pending) materialize_level(c, F);
+  res_before_write(c, F, F->d_phi);
   materialize_rhs(c, F);   // (k_prolong_smooth and the one-substep kernel read rhs as stored)
   rb_stale_above(c, lvl + 1);
   const bool split = F->has_remote;
@@ -741,6 +796,7 @@ static int correct_block3(omg_ctx* c, int l, bool res_ready, bool defer_gc = fal
   if (F->shift_pending) materialize_level(c, F);
   rb_stale_above(c, l);
   double* other = F->d_phi == F->d_data ? F->d_phi_buf : F->d_data;
+  res_before_write(c, F, other);
   const LevelView cv = C->view();
   int done = 3;
   deep_before(c, F, 0);   // (the pass reads colour 0, before the correction)
@@ -791,6 +847,7 @@ static void correct_and_fill(omg_ctx* c, int lvl, bool then_gsrb = false, bool s
   Level* C = level_ptr(c, lvl);
   if (save_old && (then_gsrb || !correct_fill_fused(c, lvl)))
     throw OmgError("internal: old = phi fused into an unfused correction");
+  if (F) res_before_write(c, F, F->d_phi);
   rb_stale_above(c, lvl + 1);
   if (correct_fill_fused(c, lvl)) {
     // every parent here has all its children on this GPU (no prolongation
@@ -953,6 +1010,20 @@ double fas_vcycle(omg_ctx* c, int highest_lvl, bool want_max_res, bool standalon
   const bool has_highest = highest_lvl >= c->lowest;
   const int min_lvl = c->lowest, max_lvl = has_highest ? highest_lvl : c->highest;
   const bool full = standalone && !has_highest;   // a stand-alone cycle over the whole tree
+  // A res left pending by the previous stand-alone cycle (materialize_res) is
+  // dead when this cycle's update_coarse runs on that level, which writes
+  // every box of it (or leaves it pending anew); decided here, before this
+  // cycle's rhs mean joins the list and its first pass writes the buffer.
+  // Any other cycle (partial, inside FMG, or one whose coarse tail holds the
+  // level) leaves that res as the reference does: it is stored first.
+  {
+    const int tt = tail_top(c, max_lvl);
+    const bool top_updates = full && max_lvl > min_lvl && !(tt >= min_lvl && !c->no_tail && max_lvl <= tt);
+    for (auto& kv : c->levels) {
+      if (top_updates && kv.first == max_lvl) kv.second.res_pend = false;
+      else materialize_res(c, &kv.second);
+    }
+  }
   // a pending phi shift (previous stand-alone cycle) is absorbed by the first
   // substep on max_lvl or dropped where restriction overwrites a level
   if (c->phi_shift_pending) {
@@ -1029,7 +1100,7 @@ double fas_vcycle(omg_ctx* c, int highest_lvl, bool want_max_res, bool standalon
     // (update_coarse reads the level's ghosts: no smoothing above consumed a
     // deferral, e.g. a cycle that is not stand-alone with n_cycle_down = 0)
     if (Level* Fd = level_ptr(c, l); Fd && Fd->gc_deferred) fill_gc_lvl(c, l, 1);
-    update_coarse(c, l, fused, tail_crhs && l == top + 1);
+    update_coarse(c, l, fused, tail_crhs && l == top + 1, full && l == max_lvl);
     faces_join(c, level_ptr(c, l));   // (update_coarse joined them; defensive)
   }
   if (tail) {
@@ -1092,6 +1163,7 @@ double fas_vcycle(omg_ctx* c, int highest_lvl, bool want_max_res, bool standalon
 
 // mg_fas_fmg (m_multigrid.f90:84-147)
 double fas_fmg(omg_ctx* c, bool have_guess, bool want_max_res) {
+  materialize_res_all(c);   // (FMG's own update_coarse loop stores; a pending res is written out as it stands)
   materialize_rhs_all(c);
   if (have_guess) {
     materialize_phi(c);
@@ -1178,6 +1250,10 @@ static void graph_rollback(omg_ctx* c, int key, const std::map<int, double*>& ph
 
 double run_cycle(omg_ctx* c, int key, const std::function<double()>& body) {
   if (!graph_ok(c)) return body();
+  // a captured cycle leaves no res pending (res_pend_ok) and finds none: what
+  // a direct cycle left is stored before the capture begins, so a rollback
+  // has no such state to restore
+  materialize_res_all(c);
   std::map<int, double*> phi_at_start;
   for (auto& kv : c->levels) phi_at_start[kv.first] = kv.second.d_phi;
   c->capturing = true;
@@ -1242,6 +1318,8 @@ void set_operator(omg_ctx* c, int op, double lambda) {
     throw OmgError("vlaplacian/vhelmholtz_set_methods: mg%n_extra_vars == 0");
   if (op == OMG_VLAPLACIAN) lambda = 0.0;
   const bool changed = c->op != op;
+  // (a pending res is that of the operator and lambda it was skipped under)
+  if ((changed || lambda != c->lambda) && !c->host_only) materialize_res_all(c);
   if (changed) rhs_pend_retry(c);
   c->op = op;
   c->lambda = lambda;

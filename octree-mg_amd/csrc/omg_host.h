@@ -259,7 +259,14 @@ void residual_lvl(omg_ctx* c, int lvl, unsigned long long* maxbits);
 double max_residual_lvl(omg_ctx* c, int lvl);
 void restrict_lvl(omg_ctx* c, int iv, int lvl);
 void prolong(omg_ctx* c, int lvl, int iv, int iv_to, int add);
-void update_coarse(omg_ctx* c, int lvl, bool fused = false, bool tail_crhs = false);
+// res_may_pend: the caller is a stand-alone cycle on its top level, whose
+// stored res nothing reads before it is overwritten (Level::res_pend)
+void update_coarse(omg_ctx* c, int lvl, bool fused = false, bool tail_crhs = false, bool res_may_pend = false);
+// a level's res left unstored by update_coarse: written out / before a write
+// of the phi buffer `buf` of the level that it would be recomputed from
+void materialize_res(omg_ctx* c, Level* L);
+void materialize_res_all(omg_ctx* c);
+void res_before_write(omg_ctx* c, Level* L, const double* buf);
 void correct_children(omg_ctx* c, int lvl);
 void check_finite_res(double r, const char* where);
 double fas_vcycle(omg_ctx* c, int highest_lvl, bool want_max_res, bool standalone);
@@ -283,7 +290,8 @@ void materialize_phi(omg_ctx* c);
 RhsShifts rhs_shifts(omg_ctx* c, const Level* L);
 void materialize_rhs(omg_ctx* c, Level* L);
 void materialize_rhs_all(omg_ctx* c);
-void rhs_pend_retry(omg_ctx* c);   // the smoothing counts, the smoother or the operator changed
+// the smoothing counts, the smoother or the operator changed (rhs_pend_off and res_pend_off)
+void rhs_pend_retry(omg_ctx* c);
 void drop_rhs_lex(omg_ctx* c);
 void enter(omg_ctx* c, bool writes = true);
 enum { kPlain = 0, kInCycle = 1 };

@@ -193,6 +193,16 @@ struct Level {
   // stand-alone cycle: the level's cycles subtract at once (today's pass)
   // until the smoothing counts, the smoother or the operator change
   bool rhs_pend_off = false;
+  // res of this level is still to store (materialize_res, omg_cycle.cpp): a
+  // stand-alone cycle's update_coarse ran its residual without the store, and
+  // res_src is the phi buffer (d_data or d_phi_buf) that launch read, ghost
+  // faces included; it stays unwritten until the res is stored or dropped
+  bool res_pend = false;
+  double* res_src = nullptr;
+  // a pass of a stand-alone cycle had to store the res before writing that
+  // buffer: the level's cycles store at once until the smoothing counts, the
+  // smoother or the operator change
+  bool res_pend_off = false;
   int8_t* d_nbk = nullptr;
   int* d_nba = nullptr;
   int* d_sendpos = nullptr;
@@ -390,6 +400,7 @@ struct omg_ctx {
   int rhs_n = 0;
   bool in_full_cycle = false;          // inside a stand-alone cycle over the whole tree (fas_vcycle)
   bool no_rhs_pend = false;            // OMG_NO_RHS_PEND: every cycle writes rhs - mean at once
+  bool no_res_pend = false;            // OMG_NO_RES_PEND: update_coarse always stores the level's res
   hipStream_t stream2 = nullptr;       // side stream (rhs sum chain)
   hipStream_t stream_comm = nullptr;   // halo exchange overlapped with interior boxes (highest priority)
   int comm_priority = 0;               // its priority (hipDeviceGetStreamPriorityRange's greatest)

@@ -251,7 +251,7 @@ bool launch_smooth_resid(const LevelView& F, const LevelView& C, int op, double 
 void launch_resid_restrict(const LevelView& F, const LevelView& C, int op, double lambda,
                            unsigned long long* maxbits, int restrict_on, const int* parent_local,
                            const int* dixp, hipStream_t st, const int* list = nullptr, int n_list = 0,
-                           RhsShifts rs = RhsShifts());
+                           RhsShifts rs = RhsShifts(), bool store = true);
 // sub: form the parent's res = phi - old on the fly (and store it) instead of
 // reading it (correct_children's parent loop fused in); skip1: a colour-1
 // red-black substep follows, so all-local boxes correct and push colour 0 only

@@ -104,6 +104,7 @@ void phi_mean_ready(omg_ctx* c) {
 // applied before anything else reads phi.
 void materialize_level(omg_ctx* c, Level* L) {
   if (!L->shift_pending) return;
+  res_before_write(c, L, L->d_phi);
   phi_mean_ready(c);
   L->shift_pending = false;
   rb_stale_above(c, L->lvl);
@@ -154,7 +155,7 @@ void materialize_rhs_all(omg_ctx* c) {
   for (auto& kv : c->levels) materialize_rhs(c, &kv.second);
 }
 void rhs_pend_retry(omg_ctx* c) {
-  for (auto& kv : c->levels) kv.second.rhs_pend_off = false;
+  for (auto& kv : c->levels) kv.second.rhs_pend_off = kv.second.res_pend_off = false;
 }
 // whether a cycle may leave the level's rhs - mean pending: its passes are
 // the block passes that take the list
@@ -174,6 +175,9 @@ static void drop_rhs_cache(omg_ctx* c) {
 // entry points other than the cycles: apply pending phi work first; `writes`
 // = the call may change rhs (the cached rhs sum is dropped)
 void enter(omg_ctx* c, bool writes) {
+  // (a pending res first: it is formed from phi and rhs as they stand, the
+  // shifts below subtract in place)
+  materialize_res_all(c);
   materialize_rhs_all(c);
   materialize_phi(c);
   for (auto& kv : c->levels)
@@ -189,6 +193,9 @@ void enter(omg_ctx* c, bool writes) {
 // (bit-identical), levels that restriction overwrites drop it, anything else
 // applies it first (materialize_phi).
 void subtract_mean(omg_ctx* c, int iv, int ghosts, int mode) {
+  // (a stand-alone cycle resolves a pending res at its start, before its rhs
+  // mean joins the list, and its phi pass only reads)
+  if (mode != kInCycle) materialize_res_all(c);
   // subtracting from interior and ghosts keeps same-GPU / remote face ghosts
   // equal to a fill; physical and refinement-boundary ghosts are not.
   if (iv == 1) {

@@ -27,13 +27,13 @@ constexpr int kPsBS16 = 512, kPsWaves = 8;
 constexpr int kSumsLPW = 32, kSumsR = 4;
 constexpr bool kSumsNT = true, kSubNTLd = false, kSubNTSt = false;
 
-template <int NC, int OP, int BS>
+template <int NC, int OP, int BS, bool STORE = true>
 __device__ __forceinline__ void resid_restrict_core(const LevelView& F, const LevelView& Cv, double lambda,
                                                     unsigned long long* maxbits, int restrict_on,
                                                     const int* parent_local, const int* dixp, int b, double* sb,
                                                     const v2d* fr);
 
-template <int NC, int OP, int BS>
+template <int NC, int OP, int BS, bool STORE = true>
 __device__ __forceinline__ void resid_restrict_box(const LevelView& F, const LevelView& Cv, double lambda,
                                                    unsigned long long* maxbits, int restrict_on,
                                                    const int* parent_local, const int* dixp, int b, double* sb,
@@ -64,12 +64,31 @@ __device__ __forceinline__ void resid_restrict_box(const LevelView& F, const Lev
       }
   }
   __syncthreads();
-  resid_restrict_core<NC, OP, BS>(F, Cv, lambda, maxbits, restrict_on, parent_local, dixp, b, sb, fr);
+  resid_restrict_core<NC, OP, BS, STORE>(F, Cv, lambda, maxbits, restrict_on, parent_local, dixp, b, sb, fr);
+}
+
+// k_resid_restrict without the store of res: with no stores between a thread's
+// steps the compiler schedules two steps' LDS loads together (16^3 boxes: 92
+// VGPRs against 56, a workgroup fewer per CU).  Each step's stencil offset
+// therefore takes a zero from an empty asm that reads the max of the steps
+// before, so its loads wait for their values as they did behind their stores.
+template <bool ON>
+__device__ __forceinline__ int step_zero(double mx) {
+  if constexpr (ON) {
+    int zero = 0;
+    asm volatile("" : "+v"(zero) : "v"(mx));
+    return zero;
+  } else {
+    return 0;
+  }
 }
 
 // The residual and the restriction of box b from its tile in LDS (phi with
 // its ghost faces, Tl<NC> layout) and rhs in registers (pairs q2 = tid + BS*r).
-template <int NC, int OP, int BS>
+// STORE = false: res of the box itself is not written (update_coarse on a
+// level whose stored res nothing reads, Level::res_pend); the max and the
+// restriction of phi and res are those of the storing form.
+template <int NC, int OP, int BS, bool STORE>
 __device__ __forceinline__ void resid_restrict_core(const LevelView& F, const LevelView& Cv, double lambda,
                                                     unsigned long long* maxbits, int restrict_on,
                                                     const int* parent_local, const int* dixp, int b, double* sb,
@@ -91,7 +110,8 @@ __device__ __forceinline__ void resid_restrict_core(const LevelView& F, const Le
     const int e = q2 >= HV / 2, o = 1 - e;
     Nbr7 s0, s1;
     if constexpr (HN % 2 == 0) {
-      pair_stencil<NC>(sb + o * HV, sb + 2 * HV + o * FH, FS, e, 2 * q2 - e * HV, s0, s1);
+      pair_stencil<NC>(sb + o * HV, sb + 2 * HV + o * FH, FS, e,
+                       2 * q2 - e * HV + step_zero<!STORE && (NR > 1)>(mx), s0, s1);
     } else {   // NC == 2: one cell per row
       int i, j, k;
       TL::decode(2 * q2, i, j, k);
@@ -111,7 +131,7 @@ __device__ __forceinline__ void resid_restrict_core(const LevelView& F, const Le
     const double r0 = fr[r].x - l0, r1 = fr[r].y - l1;
     mx = amax(mx, amax(fabs(r0), fabs(r1)));
     rv[r] = make_double2(r0, r1);
-    st_nt(res + 2 * q2, r0, r1);
+    if constexpr (STORE) st_nt(res + 2 * q2, r0, r1);
   }
   if (maxbits) launch_max<BS>(maxbits, mx);
   if (!restrict_on || parent_local[b] < 0) return;
@@ -146,7 +166,7 @@ __device__ __forceinline__ void resid_restrict_core(const LevelView& F, const Le
   }
 }
 
-template <int NC, int OP, int BS>
+template <int NC, int OP, int BS, bool STORE = true>
 __global__ void __launch_bounds__(BS) k_resid_restrict(LevelView F, LevelView Cv, double lambda,
                                                        unsigned long long* maxbits, int restrict_on,
                                                        const int* parent_local, const int* dixp,
@@ -154,8 +174,8 @@ __global__ void __launch_bounds__(BS) k_resid_restrict(LevelView F, LevelView Cv
                                                        int n_rsh) {
   __shared__ double sb[Tl<NC>::NST];
   const int q = xcd_box(blockIdx.x, gridDim.x, F.rev);
-  resid_restrict_box<NC, OP, BS>(F, Cv, lambda, maxbits, restrict_on, parent_local, dixp, list ? list[q] : q, sb,
-                                 rsh, n_rsh);
+  resid_restrict_box<NC, OP, BS, STORE>(F, Cv, lambda, maxbits, restrict_on, parent_local, dixp,
+                                        list ? list[q] : q, sb, rsh, n_rsh);
 }
 
 // Tile offset of the cell at layer v along axis d and tangential (a, c)
@@ -1055,15 +1075,20 @@ bool tiled_nc(int nc) { return nc == 16 || nc == 8 || nc == 4 || nc == 2; }
 
 void launch_resid_restrict(const LevelView& F, const LevelView& C, int op, double lambda,
                            unsigned long long* maxbits, int restrict_on, const int* parent_local,
-                           const int* dixp, hipStream_t st, const int* list, int n_list, RhsShifts rs) {
+                           const int* dixp, hipStream_t st, const int* list, int n_list, RhsShifts rs,
+                           bool store) {
   const int n = list ? n_list : F.n;
   if (n == 0) return;
   if (rs.n < 0 || rs.n > kRhsPendMax || (rs.n && !rs.s))
     throw std::runtime_error("launch_resid_restrict: at most kRhsPendMax pending rhs shifts");
   const dim3 g(n);
-#define OMG_RR_OP(NC, BS, OPV)                                                                                  \
-  k_resid_restrict<NC, OPV, BS><<<g, dim3(BS), 0, st>>>(F, C, lambda, maxbits, restrict_on, parent_local, dixp, \
-                                                        list, rs.s, rs.n);
+#define OMG_RR_OP(NC, BS, OPV)                                                                             \
+  if (store)                                                                                               \
+    k_resid_restrict<NC, OPV, BS, true><<<g, dim3(BS), 0, st>>>(F, C, lambda, maxbits, restrict_on,        \
+                                                                parent_local, dixp, list, rs.s, rs.n);     \
+  else                                                                                                     \
+    k_resid_restrict<NC, OPV, BS, false><<<g, dim3(BS), 0, st>>>(F, C, lambda, maxbits, restrict_on,       \
+                                                                 parent_local, dixp, list, rs.s, rs.n);
 #define OMG_RR(NC, BS) OMG_FOR_OP(op, OMG_RR_OP, NC, BS)
   switch (F.nc) {
     case 16: OMG_RR(16, 512) break;
