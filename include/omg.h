@@ -205,6 +205,51 @@ int omg_get_dense(omg_ctx *ctx, int lvl, int iv, double *dev, const long long lo
                   const long long n[3], const long long stride[3], void *stream,
                   long long *n_cells);
 
+/* The gradient of variable iv as dense windows in DEVICE memory (no reference
+ * counterpart: the reference's users take cc(i+1) - cc(i-1) over
+ * mg%boxes(id)%cc after mg_fill_ghost_cells_lvl, which is the definition
+ * here).  lo, n, stride, stream and n_cells, the clipping and the plan-only
+ * behaviour are exactly omg_get_dense's; the three component windows share
+ * them.  dev[d] is the window of component d (0 x, 1 y, 2 z); a NULL dev[d]
+ * skips that component.  For every interior cell (i,j,k) of this rank's boxes
+ * inside the window, component d is
+ *     (cc(+1 in d) - cc(-1 in d)) * f_d,   f_d = (0.5 * scale) / dr_d,
+ * f_d computed once on the host in double with the level's dr: one
+ * subtraction and one multiplication per value, no contraction (scale = -1
+ * gives the field of a potential, signed zeros included).  cc is the stored
+ * box with its face ghosts: i = 0 and nc+1 come from faces 1 and 2, j from
+ * faces 3 and 4, k from faces 5 and 6; edge and corner ghosts are never
+ * needed.  Window elements that no box of this rank covers keep their values.
+ * fill != 0: the ghost cells of iv at lvl are filled first, as
+ * omg_fill_ghost_cells_lvl fills them (physical, periodic, refinement-boundary
+ * and remote ghosts); on several ranks the call is then collective like that
+ * entry, made by every rank whatever its window.  For phi a fill that still
+ * stands is skipped.  fill == 0: the ghosts are used as they stand (a variable
+ * whose ghosts hold something on purpose, such as rhs after omg_phi_bc_store)
+ * and the call is not collective.
+ * State: the call reads like omg_get_dense (pending work on phi and rhs is
+ * applied and deferred ghosts are filled before anything is read; the host's
+ * own boxes on a replicated level); apart from the fill nothing of the state
+ * changes, and a cycle after the call gives the bits it would have given
+ * without it.
+ * Stream ordering is omg_get_dense's; a call with a cached window never
+ * waits on the host (a fill that exchanges over the loopback or host
+ * transport, or runs a host refinement-boundary callback, waits as it does
+ * anywhere).  The windows share the level's cache of four clippings with
+ * omg_put_dense / omg_get_dense: the same records, "16-B aligned" being true
+ * when every non-NULL base is.  OMG_DENSE_GENERIC=1: the per-cell kernel for
+ * every box; both kernels give the same bits.
+ * Errors (nothing is launched): a bad lvl, iv, extent or stride; all three
+ * pointers NULL with a non-empty window; a non-NULL pointer that is not
+ * device memory of the context's GPU or whose window reaches past the end of
+ * its allocation; two non-NULL components whose windows (first to last
+ * element) overlap.
+ * Profiling families: dense_grad (the call), dense_grad_row (its tile kernel). */
+int omg_get_dense_grad(omg_ctx *ctx, int lvl, int iv, double *const dev[3],
+                       const long long lo[3], const long long n[3],
+                       const long long stride[3], double scale, int fill,
+                       void *stream, long long *n_cells);
+
 /* The hot path.  omg_fas_vcycle = mg_fas_vcycle (src/m_multigrid.f90:150-243);
  * highest_lvl < lowest_lvl means "not present".  omg_fas_fmg = mg_fas_fmg
  * (:84-147).  max_res is written when want_max_res (the optional argument). */

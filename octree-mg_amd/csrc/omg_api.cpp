@@ -127,11 +127,11 @@ DensePlan& dense_plan(omg_ctx* c, Level& L, const long long* lo, const long long
   return P;
 }
 
-void dense_io(omg_ctx* c, int lvl, int iv, double* dev, const long long* lo, const long long* n,
-              const long long* stride, void* stream, long long* n_cells, bool put) {
-  const char* who = put ? "omg_put_dense" : "omg_get_dense";
-  auto fail = [&](const std::string& what) { throw OmgError(std::string(who) + ": " + what); };
-  Level* L = level_ptr(c, lvl);
+// The argument checks the dense entries share (before anything is launched):
+// level, variable and window; returns whether the window is empty.
+template <typename Fail>
+bool dense_check_window(omg_ctx* c, const Level* L, int iv, const long long* lo, const long long* n,
+                        const long long* stride, Fail&& fail) {
   if (!L) fail("no such level");
   if (iv < 1 || iv > c->n_vars) fail("bad variable index");
   if (!lo || !n || !stride) fail("lo, n and stride are required");
@@ -146,8 +146,42 @@ void dense_io(omg_ctx* c, int lvl, int iv, double* dev, const long long* lo, con
     if (stride[1] < n[0]) fail("stride[1] < n[0]");
     if (stride[2] / n[1] < stride[1]) fail("stride[2] < stride[1]*n[1]");
     if (stride[2] > LLONG_MAX / 8 / n[2]) fail("window out of range");
-    if (!dev) fail("NULL pointer with a non-empty window");
   }
+  return empty;
+}
+
+// doubles from a non-empty window's first element to one past its last
+long long dense_extent(const long long* n, const long long* stride) {
+  return (n[2] - 1) * stride[2] + (n[1] - 1) * stride[1] + n[0];
+}
+
+// the pointer must be device memory of this GPU, the window inside its allocation
+template <typename Fail>
+void dense_check_pointer(omg_ctx* c, const double* dev, const long long* n, const long long* stride, Fail&& fail) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, dev) != hipSuccess) {
+    (void)hipGetLastError();
+    fail("the pointer is not device memory");
+  }
+  if (at.type != hipMemoryTypeDevice) fail("the pointer is not device memory");
+  if (at.device != c->device) fail("the pointer belongs to another GPU than the context's");
+  hipDeviceptr_t base = nullptr;
+  size_t bytes = 0;
+  if (hipMemGetAddressRange(&base, &bytes, (hipDeviceptr_t)dev) == hipSuccess) {
+    if ((const char*)dev + (size_t)dense_extent(n, stride) * sizeof(double) > (const char*)base + bytes)
+      fail("the window reaches past the end of the pointer's allocation");
+  } else {
+    (void)hipGetLastError();
+  }
+}
+
+void dense_io(omg_ctx* c, int lvl, int iv, double* dev, const long long* lo, const long long* n,
+              const long long* stride, void* stream, long long* n_cells, bool put) {
+  const char* who = put ? "omg_put_dense" : "omg_get_dense";
+  auto fail = [&](const std::string& what) { throw OmgError(std::string(who) + ": " + what); };
+  Level* L = level_ptr(c, lvl);
+  const bool empty = dense_check_window(c, L, iv, lo, n, stride, fail);
+  if (!empty && !dev) fail("NULL pointer with a non-empty window");
   if (put && L->replicated)
     fail("level " + std::to_string(lvl) + " is replicated on every rank: use omg_upload_level");
   const bool generic = env_flag("OMG_DENSE_GENERIC");
@@ -156,25 +190,7 @@ void dense_io(omg_ctx* c, int lvl, int iv, double* dev, const long long* lo, con
     if (n_cells) *n_cells = empty ? 0 : dense_plan(c, *L, lo, n, stride, aligned, generic, L->replicated).n_cells;
     return;
   }
-  if (!empty) {
-    // the pointer must be device memory of this GPU, the window inside its allocation
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, dev) != hipSuccess) {
-      (void)hipGetLastError();
-      fail("the pointer is not device memory");
-    }
-    if (at.type != hipMemoryTypeDevice) fail("the pointer is not device memory");
-    if (at.device != c->device) fail("the pointer belongs to another GPU than the context's");
-    hipDeviceptr_t base = nullptr;
-    size_t bytes = 0;
-    if (hipMemGetAddressRange(&base, &bytes, (hipDeviceptr_t)dev) == hipSuccess) {
-      const long long extent = (n[2] - 1) * stride[2] + (n[1] - 1) * stride[1] + n[0];
-      if ((const char*)dev + (size_t)extent * sizeof(double) > (const char*)base + bytes)
-        fail("the window reaches past the end of the pointer's allocation");
-    } else {
-      (void)hipGetLastError();
-    }
-  }
+  if (!empty) dense_check_pointer(c, dev, n, stride, fail);
   if (put) {
     enter(c);
     // (before the early return, as omg_upload_level)
@@ -202,6 +218,75 @@ void dense_io(omg_ctx* c, int lvl, int iv, double* dev, const long long* lo, con
       launch_dense_row(V, iv, P.d_clips, P.n_row, dev, stride[1], stride[2], put, c->stream);
     }
     launch_dense_cell(V, iv, P.d_clips + P.n_row, P.n_gen, dev, stride[1], stride[2], put, c->stream);
+    HIPCHK(hipGetLastError());
+  }
+  if (foreign) {
+    HIPCHK(hipEventRecord(c->ev_dense_out, c->stream));
+    HIPCHK(hipStreamWaitEvent(user, c->ev_dense_out, 0));
+  }
+}
+
+// omg_get_dense_grad (kernels: omg_dense_grad.hip): omg_get_dense's window,
+// clip records and stream ordering; up to three component windows.
+void dense_grad(omg_ctx* c, int lvl, int iv, double* const* dev, const long long* lo, const long long* n,
+                const long long* stride, double scale, bool fill, void* stream, long long* n_cells) {
+  auto fail = [&](const std::string& what) { throw OmgError("omg_get_dense_grad: " + what); };
+  Level* L = level_ptr(c, lvl);
+  const bool empty = dense_check_window(c, L, iv, lo, n, stride, fail);
+  if (!dev) fail("the array of component pointers is required");
+  bool aligned = true, any = false;
+  for (int d = 0; d < 3; d++)
+    if (dev[d]) {
+      any = true;
+      aligned = aligned && ((uintptr_t)dev[d] & 15) == 0;
+    }
+  if (!empty) {
+    if (!any) fail("NULL pointers for all three components with a non-empty window");
+    const uintptr_t bytes = (uintptr_t)dense_extent(n, stride) * sizeof(double);
+    for (int d = 0; d < 3; d++)
+      for (int e = d + 1; e < 3; e++)
+        if (dev[d] && dev[e] && (uintptr_t)dev[d] < (uintptr_t)dev[e] + bytes &&
+            (uintptr_t)dev[e] < (uintptr_t)dev[d] + bytes)
+          fail("the windows of components " + std::to_string(d) + " and " + std::to_string(e) + " overlap");
+  }
+  const bool generic = env_flag("OMG_DENSE_GENERIC");
+  if (c->host_only) {
+    if (n_cells) *n_cells = empty ? 0 : dense_plan(c, *L, lo, n, stride, aligned, generic, L->replicated).n_cells;
+    return;
+  }
+  if (!empty)
+    for (int d = 0; d < 3; d++)
+      if (dev[d]) dense_check_pointer(c, dev[d], n, stride, fail);
+  // a fill of another variable than phi writes its ghosts, as omg_fill_ghost_cells_lvl
+  enter(c, fill && iv != 1);
+  // (before the early returns: the fill is collective; phi's is skipped where
+  // it stands, a decision every rank makes alike)
+  if (fill && (iv != 1 || !L->phi_gc_ok)) fill_gc_lvl(c, lvl, iv);
+  if (n_cells) *n_cells = 0;
+  if (empty || !L->n) return;
+  DensePlan& P = dense_plan(c, *L, lo, n, stride, aligned, generic, L->replicated);
+  if (n_cells) *n_cells = P.n_cells;
+  if (!P.n_cells) return;
+  if ((long long)P.n_gen * 16 > INT_MAX) fail("too many boxes for one launch");
+  DenseGrad G;
+  for (int d = 0; d < 3; d++) {
+    G.out[d] = dev[d];
+    G.f[d] = (0.5 * scale) / L->dr[d];
+  }
+  hipStream_t user = (hipStream_t)stream;
+  const bool foreign = user != c->stream;
+  if (foreign) {
+    HIPCHK(hipEventRecord(c->ev_dense_in, user));
+    HIPCHK(hipStreamWaitEvent(c->stream, c->ev_dense_in, 0));
+  }
+  {
+    Prof p(c, "dense_grad", (double)P.n_cells, lvl);
+    const LevelView V = L->view();
+    if (P.n_row) {
+      Prof pr(c, "dense_grad_row", (double)P.n_row * L->nc * L->nc * L->nc, lvl);
+      launch_dense_grad_tile(V, iv, P.d_clips, P.n_row, G, stride[1], stride[2], c->stream);
+    }
+    launch_dense_grad_cell(V, iv, P.d_clips + P.n_row, P.n_gen, G, stride[1], stride[2], c->stream);
     HIPCHK(hipGetLastError());
   }
   if (foreign) {
@@ -654,6 +739,11 @@ int omg_put_dense(omg_ctx* c, int lvl, int iv, const double* dev, const long lon
 int omg_get_dense(omg_ctx* c, int lvl, int iv, double* dev, const long long* lo, const long long* n,
                   const long long* stride, void* stream, long long* n_cells) {
   return guarded([&] { dense_io(c, lvl, iv, dev, lo, n, stride, stream, n_cells, false); });
+}
+
+int omg_get_dense_grad(omg_ctx* c, int lvl, int iv, double* const* dev, const long long* lo, const long long* n,
+                       const long long* stride, double scale, int fill, void* stream, long long* n_cells) {
+  return guarded([&] { dense_grad(c, lvl, iv, dev, lo, n, stride, scale, fill != 0, stream, n_cells); });
 }
 
 int omg_fas_vcycle(omg_ctx* c, int highest_lvl, int want_max_res, double* max_res, int standalone) {

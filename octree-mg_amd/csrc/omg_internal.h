@@ -139,6 +139,13 @@ struct DenseClip {
   long long off;
 };
 
+// omg_get_dense_grad's kernel argument: the component windows (null: the
+// component is skipped) and f_d = 0.5 * scale / dr_d.
+struct DenseGrad {
+  double* out[3];
+  double f[3];
+};
+
 // The records of one window, cached on the level: the boxes the row kernel
 // serves first (n_row), then those of the per-cell kernel (n_gen).
 struct DensePlan {

@@ -190,6 +190,15 @@ void launch_dense_row(const LevelView& L, int iv, const DenseClip* clips, int n,
                       long long s2, bool put, hipStream_t st);
 void launch_dense_cell(const LevelView& L, int iv, const DenseClip* clips, int n, double* dense, long long s1,
                        long long s2, bool put, hipStream_t st);
+// omg_get_dense_grad (omg_dense_grad.hip): the central differences of variable
+// iv, (cc(+1 in d) - cc(-1 in d)) * G.f[d], into the dense windows G.out[d]
+// (null: skipped) by the same clip records; the tile kernel takes what the
+// row kernel above takes (every non-null base 16-B aligned), the cell kernel
+// anything
+void launch_dense_grad_tile(const LevelView& L, int iv, const DenseClip* clips, int n, const DenseGrad& G,
+                            long long s1, long long s2, hipStream_t st);
+void launch_dense_grad_cell(const LevelView& L, int iv, const DenseClip* clips, int n, const DenseGrad& G,
+                            long long s1, long long s2, hipStream_t st);
 void launch_phi_bc_store(const LevelView& L, const GcBC& bc, int* nba, hipStream_t st);
 
 // The coarse end of the V-cycle in ONE single-workgroup launch (omg_tiles.hip):

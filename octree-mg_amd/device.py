@@ -44,6 +44,8 @@ SIGNATURES = {
     "omg_download_level": (_I, [_P, _I, _I, _DP]),
     "omg_put_dense": (_I, [_P, _I, _I, C.c_void_p, _LP, _LP, _LP, C.c_void_p, C.POINTER(_LL)]),
     "omg_get_dense": (_I, [_P, _I, _I, C.c_void_p, _LP, _LP, _LP, C.c_void_p, C.POINTER(_LL)]),
+    "omg_get_dense_grad": (_I, [_P, _I, _I, C.POINTER(C.c_void_p), _LP, _LP, _LP, _D, _I, C.c_void_p,
+                                C.POINTER(_LL)]),
     "omg_fas_vcycle": (_I, [_P, _I, _I, C.POINTER(_D), _I]),
     "omg_fas_fmg": (_I, [_P, _I, _I, C.POINTER(_D)]),
     "omg_apply_op": (_I, [_P, _I]),
@@ -262,6 +264,19 @@ class Context:
         """omg_get_dense: the reverse copy; window elements that no box of
         this rank covers keep their values."""
         return self._dense("get_dense", lvl, iv, ptr, lo, n, stride, stream)
+
+    def get_dense_grad(self, lvl, iv, ptrs, lo, n, stride, scale=1.0, fill=True, stream=0):
+        """omg_get_dense_grad: the central differences of variable iv,
+        (cc(+1 in d) - cc(-1 in d)) * 0.5 * scale / dr_d, into the three dense
+        windows at the device addresses ptrs = (x, y, z) (0 / None: that
+        component is skipped), which share lo, n and stride; fill: the ghost
+        cells of iv at lvl are filled first.  Returns the cells covered."""
+        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64).reshape(3)  # noqa: E731
+        dev = (C.c_void_p * 3)(*[C.c_void_p(int(p or 0) or None) for p in ptrs])
+        cells = _LL(0)
+        self.call("get_dense_grad", lvl, iv, dev, i64(lo), i64(n), i64(stride), float(scale), int(bool(fill)),
+                  C.c_void_p(int(stream) or None), C.byref(cells))
+        return cells.value
 
     def scalar(self, name, *args):
         r = _D(0.0)

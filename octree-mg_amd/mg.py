@@ -109,15 +109,21 @@ class MG(MGTree):
         self._require_alloc()
         return self.ctx.download_level(lvl, iv)
 
-    def _dense_args(self, t, what):
-        """The checks of set_dense / get_dense on a tensor [nz, ny, nx], before
-        any call into the library; returns (n, stride) in x, y, z order."""
+    @staticmethod
+    def _dense_layout(t, what):
+        """The type, dtype and stride checks of a tensor [nz, ny, nx]; returns
+        (n, stride) in x, y, z order."""
         import torch
         if not isinstance(t, torch.Tensor) or t.dim() != 3:
             raise ValueError(f"{what}: a torch tensor [nz, ny, nx] is required")
         if t.dtype != torch.float64:
             raise ValueError(f"{what}: dtype {t.dtype}, torch.float64 is required")
-        n, stride = dense_strides(t, what)
+        return dense_strides(t, what)
+
+    def _dense_args(self, t, what):
+        """The checks of set_dense / get_dense on a tensor [nz, ny, nx], before
+        any call into the library; returns (n, stride) in x, y, z order."""
+        n, stride = self._dense_layout(t, what)
         if not t.is_cuda:
             raise ValueError(f"{what}: the tensor is on {t.device}, not on the context's GPU")
         self._require_alloc()
@@ -160,6 +166,58 @@ class MG(MGTree):
         n, stride = self._dense_args(out, "get_dense")
         cells = self.ctx.get_dense(lvl, iv, out.data_ptr(), lo, n, stride,
                                    torch.cuda.current_stream(out.device).cuda_stream)
+        return out, cells
+
+    def get_dense_grad(self, lvl, iv=1, out=None, lo=(0, 0, 0), shape=None, scale=1.0, fill=True,
+                       components=(True, True, True)):
+        """omg_get_dense_grad: the central differences of variable iv at lvl,
+        component d = (cc(+1 in d) - cc(-1 in d)) * 0.5 * scale / dr_d over the
+        boxes and their ghost cells (scale = -1.0: the field of a potential),
+        as dense windows that start at the 0-based cell lo = (x, y, z).
+        `out` is a torch.float64 tensor [3, nz, ny, nx] on the context's GPU
+        (x, y, z components; default: torch.empty of shape = (nz, ny, nx), the
+        level's whole cell grid from lo when None), or a sequence of three
+        tensors [nz, ny, nx] or Nones of one shape and one set of strides; the
+        layout checks are set_dense's.  A component that is None or whose entry
+        of `components` is false is skipped and its tensor left untouched.
+        fill: the ghost cells of iv at lvl are filled first (collective on
+        several ranks); without it they are used as they stand.  Elements that
+        no box of this rank covers keep their values.  Ordered on torch's
+        current stream.  Returns (out, cells covered)."""
+        import torch
+        what = "get_dense_grad"
+        if len(components) != 3:
+            raise ValueError(f"{what}: components takes three flags")
+        if out is None:
+            self._require_alloc()
+            if shape is None:
+                g = self.level_grid(lvl)
+                shape = tuple(max(g[2 - q] - int(lo[2 - q]), 0) for q in range(3))
+            dev = self.ctx.device
+            out = torch.empty((3,) + tuple(int(v) for v in shape), dtype=torch.float64,
+                              device=torch.device("cuda", dev if dev >= 0 else torch.cuda.current_device()))
+        if isinstance(out, torch.Tensor):
+            if out.dim() != 4 or out.shape[0] != 3:
+                raise ValueError(f"{what}: a torch tensor [3, nz, ny, nx] is required")
+            parts = [out[d] for d in range(3)]
+        else:
+            parts = list(out)
+            if len(parts) != 3:
+                raise ValueError(f"{what}: three tensors (or None) are required")
+        parts = [t if components[d] else None for d, t in enumerate(parts)]
+        used = [t for t in parts if t is not None]
+        if not used:
+            raise ValueError(f"{what}: no component is asked for")
+        layouts = [self._dense_layout(t, what) for t in used]
+        if any(a != layouts[0] for a in layouts):
+            raise ValueError(f"{what}: the components differ in shape or strides")
+        for t in used:
+            self._dense_args(t, what)
+        if any(t.device != used[0].device for t in used):
+            raise ValueError(f"{what}: the components are on different devices")
+        n, stride = layouts[0]
+        cells = self.ctx.get_dense_grad(lvl, iv, [0 if t is None else t.data_ptr() for t in parts], lo, n, stride,
+                                        scale, fill, torch.cuda.current_stream(used[0].device).cuda_stream)
         return out, cells
 
     def _require_alloc(self):
