@@ -250,6 +250,83 @@ int omg_get_dense_grad(omg_ctx *ctx, int lvl, int iv, double *const dev[3],
                        const long long stride[3], double scale, int fill,
                        void *stream, long long *n_cells);
 
+/* Stream-ordered device block I/O for block-AMR hosts: the device equivalent
+ * of the reference's coupling copies (coupling_amrvac/mod_multigrid_coupling.t:
+ * mg_copy_to_tree :133-171, mg_copy_from_tree :206-234 and
+ * mg_copy_from_tree_gc :238-267, three loops over the rank's leaf blocks).
+ * Variable iv of a list of this rank's boxes, on any mixture of levels, <->
+ * the caller's block pool in DEVICE memory of the context's GPU, with no host
+ * copy and no host wait.
+ * ids[n_boxes] and box_off[n_boxes] are host arrays; ids are the reference's
+ * 1-based global box ids, in any order.  Element (i,j,k) of box q is
+ *     dev[box_off[q] + (i-1) + (j-1)*stride[1] + (k-1)*stride[2]],
+ * so box_off[q] is the offset, in doubles, of the box's interior cell (1,1,1).
+ * The strides are shared by all boxes; stride[0] must be 1 and, with
+ * m = nc_max + 2*ghost (nc_max: the largest box size listed), stride[1] >= m
+ * and stride[2] >= stride[1]*m.
+ * What moves: ghost == 0 the nc^3 interior cells 1 <= i,j,k <= nc; ghost == 1
+ * additionally the six face-ghost layers (i = 0 and nc+1 with 1 <= j,k <= nc,
+ * likewise for j and k), the ghost cells the device stores.  Edge and corner
+ * elements of a block are never read on put and never written on get (as
+ * mg_copy_from_tree_gc: "corner ghost cells not used/set").  Elements of dev
+ * outside these cells keep their values, boxes not listed keep theirs.
+ * Blocks of different boxes may interleave (blocks laid out as a dense grid
+ * do, legitimately): overlap between them is the caller's responsibility.
+ * *n_cells (if non-NULL) = the cells copied, sum of nc^3 + ghost*6*nc^2,
+ * counted on the host; a plan-only context (OMG_DEVICE_NONE) validates, counts
+ * and copies nothing.
+ * stream: exactly omg_put_dense's ordering on the caller's hipStream_t.
+ * State, omg_put_boxes: a writer like omg_upload_level (pending work on phi is
+ * applied first, derived copies of rhs are dropped).  A put of phi (iv = 1)
+ * makes the phi ghosts of EVERY level stale, since a rank cannot know which
+ * levels its peers list, and is collective in the sense of an upload of phi:
+ * every rank calls it, with n_boxes == 0 where it has nothing.  ghost == 0
+ * leaves the ghost slots alone (a put into rhs keeps what omg_phi_bc_store
+ * stored there); ghost == 1 writes the face slots as omg_upload_level does.
+ * A box on a replicated level is refused (use omg_upload_level).
+ * State, omg_get_boxes: reads like omg_download_level (pending shifts are
+ * applied, deferred ghosts filled and a pending res formed before anything is
+ * read); on a replicated level only the host's own boxes are accepted.
+ * fill != 0: the ghost cells of iv are filled first on every level, as
+ * omg_fill_ghost_cells(ctx, iv) fills them (for phi a fill that still stands
+ * is skipped per level); with several ranks the call is then collective,
+ * whatever a rank lists.  fill == 0: the ghosts are used as they stand and the
+ * call is not collective.  Apart from the fill nothing of the state changes: a
+ * cycle after the call gives the bits it would have given without it.
+ * Errors (nothing is launched, no state is touched): a bad iv, ghost or
+ * stride, a negative n_boxes; NULL ids, box_off or dev with n_boxes > 0; an id
+ * out of range, not owned by this rank or listed twice; |box_off| or a stride
+ * beyond 2^40; a pointer that is not device memory of the context's GPU; a
+ * block whose first or last touched element lies outside the pointer's
+ * allocation (where hipMemGetAddressRange answers).
+ * The records of a call (local box, level, offset; grouped by level, one
+ * launch group per level that occurs) are cached on the context for the four
+ * most recent lists; the key is n_boxes, ghost, the strides, whether the base
+ * is 16-B aligned, and the contents of ids and box_off compared by value (the
+ * switches below choose the kernel at launch: the records do not depend on
+ * them).  A call with a cached list uploads nothing and never
+ * waits on the host (a time loop repeats its list until a regrid); a new list
+ * uploads its records from pinned memory in stream order; a fifth list
+ * replaces the oldest, and that call waits for the context's stream first.
+ * omg_tree_setup drops the cache.
+ * Kernels: a tile kernel for 16^3 and 8^3 boxes, a per-cell kernel for every
+ * other size, for a level of which fewer than 1536 boxes are listed and for a
+ * get of interiors into rows with a gap between them (stride[1] > nc) of more
+ * than 6144 * 16^3 cells, where it measured faster; both give the same bits.
+ * Environment, read per call, for A/B timing and cross-checks:
+ * OMG_BOXES_GENERIC=1 the per-cell kernel for every box; OMG_BOXES_TILE=1 the
+ * tile kernel wherever it can serve; OMG_BOXES_ODD=8 / 16 the tile kernel's
+ * variant for blocks that are not 16-B aligned (8-B accesses, or 16-B
+ * accesses shifted by one cell, the default for a get with ghosts).
+ * Profiling families: boxes_put, boxes_get (the call), boxes_put_tile,
+ * boxes_get_tile (the tile kernel, per level). */
+int omg_put_boxes(omg_ctx *ctx, int iv, int n_boxes, const int *ids, const double *dev,
+                  const long long *box_off, const long long stride[3], int ghost,
+                  void *stream, long long *n_cells);
+int omg_get_boxes(omg_ctx *ctx, int iv, int n_boxes, const int *ids, double *dev,
+                  const long long *box_off, const long long stride[3], int ghost, int fill,
+                  void *stream, long long *n_cells);
+
 /* The hot path.  omg_fas_vcycle = mg_fas_vcycle (src/m_multigrid.f90:150-243);
  * highest_lvl < lowest_lvl means "not present".  omg_fas_fmg = mg_fas_fmg
  * (:84-147).  max_res is written when want_max_res (the optional argument). */

@@ -295,6 +295,231 @@ void dense_grad(omg_ctx* c, int lvl, int iv, double* const* dev, const long long
   }
 }
 
+// --- device block I/O (omg_put_boxes / omg_get_boxes, kernels: omg_boxes.hip)
+// What tools/box_io_bench.py measured, in place of switches:
+// blocks that are not 16-B aligned take the tile kernel's 8-B variant, except
+// a get with ghosts, whose interior rows the shifted variant covers with
+// whole pairs (OMG_BOXES_ODD=8 / 16 overrides, for A/B timing).  The per-cell kernel
+// takes a level with fewer listed boxes than kBoxesTileMin (one workgroup per
+// box leaves the GPU short of work: it won at 512 and 960 boxes, the tile
+// kernel from 1728 on), and a get of interiors into rows with a gap between
+// them (stride[1] > nc) of more than kBoxesGapGetCells cells (it won at 8000
+// boxes of 16^3 and more, the tile kernel at 4096, whose pool the Infinity
+// Cache still holds).  OMG_BOXES_TILE=1: the tile kernel wherever it can serve.
+constexpr int kBoxesTileMin = 1536;
+constexpr long long kBoxesGapGetCells = 6144LL * 4096;
+
+bool boxes_odd8(bool put, int ghost) {
+  const char* v = getenv("OMG_BOXES_ODD");
+  if (v && !std::strcmp(v, "8")) return true;
+  if (v && !std::strcmp(v, "16")) return false;
+  return put || !ghost;
+}
+
+// The records of a list: every id checked (range, owner, replicated level,
+// listed once), grouped by level.  Touches nothing of the context.
+template <typename Fail>
+void boxes_build(omg_ctx* c, BoxPlan& P, int n_boxes, const int* ids, const long long* box_off, bool put,
+                 Fail&& fail) {
+  P.ids.assign(ids, ids + n_boxes);
+  P.off.assign(box_off, box_off + n_boxes);
+  P.recs.resize(n_boxes);
+  std::map<int, int> per_lvl;   // level -> boxes listed
+  std::vector<int> sorted(ids, ids + n_boxes);
+  std::sort(sorted.begin(), sorted.end());
+  for (int q = 0; q < n_boxes; q++) {
+    const int id = sorted[q];
+    if (id < 1 || id > c->n_boxes) fail("box id " + std::to_string(id) + " is out of range");
+    if (q && sorted[q - 1] == id) fail("box id " + std::to_string(id) + " is listed twice");
+  }
+  for (int q = 0; q < n_boxes; q++) {
+    const int id = ids[q], lvl = c->lvl[id - 1];
+    const Level* L = level_ptr(c, lvl);
+    if (!L || c->local_index[id] < 0) fail("box id " + std::to_string(id) + " is not owned by this rank");
+    if (L->replicated) {
+      if (put) fail("level " + std::to_string(lvl) + " is replicated on every rank: use omg_upload_level");
+      if (c->rank_of[id - 1] != c->rank)
+        fail("box id " + std::to_string(id) + " on the replicated level " + std::to_string(lvl) +
+             " is not one of this rank's own boxes");
+      P.any_replicated = true;
+    }
+    if (box_off[q] > kDenseMax || box_off[q] < -kDenseMax) fail("box_off out of range");
+    per_lvl[lvl]++;
+  }
+  int first = 0;
+  for (auto& kv : per_lvl) {
+    const Level* L = level_ptr(c, kv.first);
+    BoxGroup G;
+    G.lvl = kv.first;
+    G.first = first;
+    G.n = 0;
+    P.groups.push_back(G);
+    first += kv.second;
+    P.nc_max = std::max(P.nc_max, L->nc);
+  }
+  bool have_ext = false;
+  for (int q = 0; q < n_boxes; q++) {
+    const int id = ids[q], lvl = c->lvl[id - 1];
+    const Level* L = level_ptr(c, lvl);
+    BoxGroup& G = *std::find_if(P.groups.begin(), P.groups.end(), [&](const BoxGroup& g) { return g.lvl == lvl; });
+    P.recs[G.first + G.n++] = BoxRec{c->local_index[id], lvl, box_off[q]};
+    if (!P.aligned || (box_off[q] | P.stride[1] | P.stride[2]) & 1) G.odd = true;
+    const long long nc = L->nc;
+    P.n_cells += nc * nc * nc + (long long)P.ghost * 6 * nc * nc;
+    // first and last touched element: (1,1,0) and (nc,nc,nc+1) with ghosts
+    const long long lo = box_off[q] - (P.ghost ? P.stride[2] : 0);
+    const long long hi = box_off[q] + (nc - 1) + (nc - 1) * P.stride[1] + (nc - 1 + P.ghost) * P.stride[2];
+    P.lo_ext = have_ext ? std::min(P.lo_ext, lo) : lo;
+    P.hi_ext = have_ext ? std::max(P.hi_ext, hi) : hi;
+    have_ext = true;
+  }
+}
+
+void box_io(omg_ctx* c, int iv, int n_boxes, const int* ids, double* dev, const long long* box_off,
+            const long long* stride, int ghost, bool fill, void* stream, long long* n_cells, bool put) {
+  const char* who = put ? "omg_put_boxes" : "omg_get_boxes";
+  auto fail = [&](const std::string& what) { throw OmgError(std::string(who) + ": " + what); };
+  if (iv < 1 || iv > c->n_vars) fail("bad variable index");
+  if (ghost != 0 && ghost != 1) fail("ghost must be 0 or 1");
+  if (n_boxes < 0) fail("negative n_boxes");
+  if (!stride) fail("stride is required");
+  if (stride[0] != 1) fail("stride[0] must be 1");
+  if (stride[1] < 1 || stride[2] < 1 || stride[1] > kDenseMax || stride[2] > kDenseMax) fail("stride out of range");
+  if (n_boxes > 0 && (!ids || !box_off)) fail("NULL ids or box_off with n_boxes > 0");
+  if (n_boxes > 0 && !dev) fail("NULL pointer with n_boxes > 0");
+  if (c->levels.empty()) fail("no tree (omg_tree_setup)");
+  // (the switches choose the kernel at launch: the records do not depend on them)
+  const bool generic = env_flag("OMG_BOXES_GENERIC"), force_tile = env_flag("OMG_BOXES_TILE");
+  const bool odd8 = boxes_odd8(put, ghost);
+  const bool aligned = ((uintptr_t)dev & 15) == 0;
+  // a cached list was checked when it was built
+  BoxPlan* P = nullptr;
+  for (auto& Q : c->box_plans)
+    if ((int)Q.ids.size() == n_boxes && Q.ghost == ghost && std::equal(stride, stride + 3, Q.stride) &&
+        Q.aligned == aligned && std::equal(ids, ids + n_boxes, Q.ids.begin()) &&
+        std::equal(box_off, box_off + n_boxes, Q.off.begin()))
+      P = &Q;
+  BoxPlan fresh;
+  if (P) {
+    if (put && P->any_replicated) {
+      for (int q = 0; q < n_boxes; q++)
+        if (level_ptr(c, c->lvl[ids[q] - 1])->replicated)
+          fail("level " + std::to_string(c->lvl[ids[q] - 1]) + " is replicated on every rank: use omg_upload_level");
+    }
+  } else {
+    fresh.ghost = ghost;
+    std::copy(stride, stride + 3, fresh.stride);
+    fresh.aligned = aligned;
+    boxes_build(c, fresh, n_boxes, ids, box_off, put, fail);
+  }
+  const BoxPlan& R = P ? *P : fresh;
+  if (n_boxes > 0) {
+    const long long m = R.nc_max + 2 * ghost;
+    if (stride[1] < m) fail("stride[1] < nc + 2*ghost");
+    if (stride[2] / m < stride[1]) fail("stride[2] < stride[1]*(nc + 2*ghost)");
+  }
+  if (c->host_only) {
+    if (n_cells) *n_cells = R.n_cells;
+    return;
+  }
+  if (n_boxes > 0) {
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, dev) != hipSuccess) {
+      (void)hipGetLastError();
+      fail("the pointer is not device memory");
+    }
+    if (at.type != hipMemoryTypeDevice) fail("the pointer is not device memory");
+    if (at.device != c->device) fail("the pointer belongs to another GPU than the context's");
+    hipDeviceptr_t base = nullptr;
+    size_t bytes = 0;
+    if (hipMemGetAddressRange(&base, &bytes, (hipDeviceptr_t)dev) == hipSuccess) {
+      // (in doubles from the allocation's base: |offsets| <= 20 * 2^40)
+      const long long d0 = (long long)(((const char*)dev - (const char*)base) / 8);
+      const long long rem = ((const char*)dev - (const char*)base) % 8;
+      if (d0 + R.lo_ext < 0) fail("a block starts before the pointer's allocation");
+      if ((unsigned long long)(d0 + R.hi_ext + 1) * 8 + (unsigned long long)rem > bytes)
+        fail("a block reaches past the end of the pointer's allocation");
+    } else {
+      (void)hipGetLastError();
+    }
+    for (const BoxGroup& G : R.groups)
+      if ((long long)G.n * 16 > INT_MAX) fail("too many boxes for one launch");
+  }
+  // --- nothing of the state was touched up to here
+  if (put) {
+    enter(c);
+    // (every level: a rank cannot know which levels its peers list, and the
+    // stand-alone fill decision must fall alike on every rank)
+    if (iv == 1) phi_dirty_all(c);
+  } else {
+    // a fill of another variable than phi writes its ghosts, as omg_fill_ghost_cells
+    enter(c, fill && iv != 1);
+    if (fill)
+      for (int l = c->lowest; l <= c->highest; l++) {
+        const Level* L = level_ptr(c, l);
+        if (iv != 1 || !L || !L->phi_gc_ok) fill_gc_lvl(c, l, iv);
+      }
+  }
+  if (n_cells) *n_cells = R.n_cells;
+  if (n_boxes == 0) return;
+  if (!P) {
+    if ((int)c->box_plans.size() < kBoxPlans) c->box_plans.emplace_back();
+    BoxPlan& S = *std::min_element(c->box_plans.begin(), c->box_plans.end(),
+                                   [](const BoxPlan& a, const BoxPlan& b) { return a.age < b.age; });
+    // (the oldest list makes room: its records may still be on their way to
+    // the device or being read there; the only host wait of these entries)
+    if (S.d_recs) host_sync(c, c->stream);
+    fresh.h_recs = S.h_recs;
+    fresh.d_recs = S.d_recs;
+    fresh.cap = S.cap;
+    S = std::move(fresh);
+    if (S.recs.size() > S.cap) {
+      dfree(S.d_recs);
+      if (S.h_recs) HIPCHK(hipHostFree(S.h_recs));
+      S.h_recs = nullptr;
+      S.cap = 0;
+      HIPCHK(hipHostMalloc((void**)&S.h_recs, sizeof(BoxRec) * S.recs.size()));
+      HIPCHK(hipMalloc(&S.d_recs, sizeof(BoxRec) * S.recs.size()));
+      S.cap = S.recs.size();
+    }
+    // from pinned memory, in stream order ahead of the kernels: no host wait
+    std::copy(S.recs.begin(), S.recs.end(), S.h_recs);
+    HIPCHK(hipMemcpyAsync(S.d_recs, S.h_recs, sizeof(BoxRec) * S.recs.size(), hipMemcpyHostToDevice, c->stream));
+    P = &S;
+  }
+  P->age = ++c->dense_age;
+  hipStream_t user = (hipStream_t)stream;
+  const bool foreign = user != c->stream;
+  if (foreign) {
+    HIPCHK(hipEventRecord(c->ev_dense_in, user));
+    HIPCHK(hipStreamWaitEvent(c->stream, c->ev_dense_in, 0));
+  }
+  {
+    Prof p(c, put ? "boxes_put" : "boxes_get", (double)P->n_cells);
+    for (const BoxGroup& G : P->groups) {
+      const Level* L = level_ptr(c, G.lvl);
+      const LevelView V = L->view();
+      const double cells = (double)G.n * ((double)L->nc * L->nc * L->nc + ghost * 6.0 * L->nc * L->nc);
+      const bool tile = !generic && boxes_tile_nc(L->nc) &&
+                        (force_tile || (G.n >= kBoxesTileMin && (put || ghost || stride[1] == L->nc ||
+                                                                 (long long)G.n * L->nc * L->nc * L->nc <=
+                                                                     kBoxesGapGetCells)));
+      if (tile) {
+        Prof pr(c, put ? "boxes_put_tile" : "boxes_get_tile", cells, G.lvl);
+        launch_boxes_tile(V, iv, P->d_recs + G.first, G.n, dev, stride[1], stride[2], ghost, put, odd8 && G.odd,
+                          c->stream);
+      } else {
+        launch_boxes_cell(V, iv, P->d_recs + G.first, G.n, dev, stride[1], stride[2], ghost, put, c->stream);
+      }
+    }
+    HIPCHK(hipGetLastError());
+  }
+  if (foreign) {
+    HIPCHK(hipEventRecord(c->ev_dense_out, c->stream));
+    HIPCHK(hipStreamWaitEvent(user, c->ev_dense_out, 0));
+  }
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -744,6 +969,18 @@ int omg_get_dense(omg_ctx* c, int lvl, int iv, double* dev, const long long* lo,
 int omg_get_dense_grad(omg_ctx* c, int lvl, int iv, double* const* dev, const long long* lo, const long long* n,
                        const long long* stride, double scale, int fill, void* stream, long long* n_cells) {
   return guarded([&] { dense_grad(c, lvl, iv, dev, lo, n, stride, scale, fill != 0, stream, n_cells); });
+}
+
+int omg_put_boxes(omg_ctx* c, int iv, int n_boxes, const int* ids, const double* dev, const long long* box_off,
+                  const long long* stride, int ghost, void* stream, long long* n_cells) {
+  return guarded([&] {
+    box_io(c, iv, n_boxes, ids, const_cast<double*>(dev), box_off, stride, ghost, false, stream, n_cells, true);
+  });
+}
+
+int omg_get_boxes(omg_ctx* c, int iv, int n_boxes, const int* ids, double* dev, const long long* box_off,
+                  const long long* stride, int ghost, int fill, void* stream, long long* n_cells) {
+  return guarded([&] { box_io(c, iv, n_boxes, ids, dev, box_off, stride, ghost, fill != 0, stream, n_cells, false); });
 }
 
 int omg_fas_vcycle(omg_ctx* c, int highest_lvl, int want_max_res, double* max_res, int standalone) {

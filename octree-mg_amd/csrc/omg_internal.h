@@ -160,6 +160,42 @@ struct DensePlan {
 };
 constexpr int kDensePlans = 4;
 
+// Device block I/O (omg_put_boxes / omg_get_boxes, omg_boxes.hip): one record
+// per listed box: the local box at its level and the offset, in doubles, of
+// its interior cell (1,1,1) in the caller's pool.
+struct BoxRec {
+  int box;
+  int lvl;
+  long long off;
+};
+
+// The records of one list, cached on the context, grouped by level: one
+// launch group per level that occurs.
+struct BoxGroup {
+  int lvl = 0, first = 0, n = 0;
+  bool odd = false;    // some row of some block is not 16-B aligned
+};
+struct BoxPlan {
+  // the key: the list by value, the strides, ghost and whether the base is
+  // 16-B aligned
+  std::vector<int> ids;
+  std::vector<long long> off;
+  long long stride[3] = {0, 0, 0};
+  int ghost = 0;
+  bool aligned = false;
+  std::vector<BoxRec> recs;         // (grouped; uploaded through h_recs)
+  std::vector<BoxGroup> groups;
+  bool any_replicated = false;      // some box lies on a replicated level (a put is refused)
+  int nc_max = 0;
+  long long lo_ext = 0, hi_ext = 0; // first and last touched element, relative to the base
+  BoxRec* h_recs = nullptr;         // pinned: the source of the stream-ordered upload
+  BoxRec* d_recs = nullptr;
+  size_t cap = 0;
+  long long n_cells = 0;
+  long long age = 0;
+};
+constexpr int kBoxPlans = 4;
+
 struct Level {
   int lvl = 0, nc = 0, n = 0;
   long long stride = 0;
@@ -415,6 +451,7 @@ struct omg_ctx {
   hipEvent_t ev_main = nullptr, ev_side = nullptr, ev_phi = nullptr;
   hipEvent_t ev_dense_in = nullptr, ev_dense_out = nullptr;   // omg_put_dense / omg_get_dense: the caller's stream
   long long dense_age = 0;
+  std::vector<omg::BoxPlan> box_plans;   // lists of omg_put_boxes / omg_get_boxes (at most kBoxPlans)
   bool phi_mean_on_side = false;
   bool no_tail = false;                // OMG_NO_TAIL: level-by-level coarse end (A/B checks)
   bool no_fuse_up = false;             // OMG_NO_FUSE_UP: separate prolongation and first up-substep

@@ -190,6 +190,18 @@ void launch_dense_row(const LevelView& L, int iv, const DenseClip* clips, int n,
                       long long s2, bool put, hipStream_t st);
 void launch_dense_cell(const LevelView& L, int iv, const DenseClip* clips, int n, double* dense, long long s1,
                        long long s2, bool put, hipStream_t st);
+// device block I/O (omg_boxes.hip): variable iv of the boxes of one level
+// listed by records (BoxRec) <-> blocks of the caller's pool, element (i,j,k)
+// at dev[rec.off + (i-1) + (j-1)*s1 + (k-1)*s2]; ghost = 1: with the six
+// face-ghost layers.  The tile kernel takes boxes of boxes_tile_nc() sizes at
+// any alignment (w8: 8-B accesses on the caller's side instead of shifted
+// 16-B ones), the per-cell kernel any box.
+bool boxes_tile_nc(int nc);
+int boxes_cell_bpc(int nc, int ghost);   // workgroups per record of the per-cell kernel
+void launch_boxes_tile(const LevelView& L, int iv, const BoxRec* recs, int n, double* dev, long long s1,
+                       long long s2, int ghost, bool put, bool w8, hipStream_t st);
+void launch_boxes_cell(const LevelView& L, int iv, const BoxRec* recs, int n, double* dev, long long s1,
+                       long long s2, int ghost, bool put, hipStream_t st);
 // omg_get_dense_grad (omg_dense_grad.hip): the central differences of variable
 // iv, (cc(+1 in d) - cc(-1 in d)) * G.f[d], into the dense windows G.out[d]
 // (null: skipped) by the same clip records; the tile kernel takes what the

@@ -188,6 +188,11 @@ void ensure_rhs_lex(omg_ctx* c) {
 // 16-69, m_prolong.f90:16-48).
 void free_levels(omg_ctx* c) {
   free_state_destroy(c);   // the FFT level belongs to the old tree
+  for (auto& P : c->box_plans) {   // (the lists name boxes of the old tree)
+    dfree(P.d_recs);
+    if (P.h_recs) (void)hipHostFree(P.h_recs);
+  }
+  c->box_plans.clear();
   for (auto& kv : c->levels) {
     Level& L = kv.second;
     dfree(L.d_data); L.d_phi = nullptr; dfree(L.d_nbk); dfree(L.d_nba); dfree(L.d_sendpos); dfree(L.d_rb);

@@ -46,6 +46,9 @@ SIGNATURES = {
     "omg_get_dense": (_I, [_P, _I, _I, C.c_void_p, _LP, _LP, _LP, C.c_void_p, C.POINTER(_LL)]),
     "omg_get_dense_grad": (_I, [_P, _I, _I, C.POINTER(C.c_void_p), _LP, _LP, _LP, _D, _I, C.c_void_p,
                                 C.POINTER(_LL)]),
+    "omg_put_boxes": (_I, [_P, _I, _I, C.c_void_p, C.c_void_p, C.c_void_p, _LP, _I, C.c_void_p, C.POINTER(_LL)]),
+    "omg_get_boxes": (_I, [_P, _I, _I, C.c_void_p, C.c_void_p, C.c_void_p, _LP, _I, _I, C.c_void_p,
+                           C.POINTER(_LL)]),
     "omg_fas_vcycle": (_I, [_P, _I, _I, C.POINTER(_D), _I]),
     "omg_fas_fmg": (_I, [_P, _I, _I, C.POINTER(_D)]),
     "omg_apply_op": (_I, [_P, _I]),
@@ -277,6 +280,33 @@ class Context:
         self.call("get_dense_grad", lvl, iv, dev, i64(lo), i64(n), i64(stride), float(scale), int(bool(fill)),
                   C.c_void_p(int(stream) or None), C.byref(cells))
         return cells.value
+
+    def _boxes(self, name, iv, ids, ptr, box_off, stride, ghost, extra, stream):
+        # (ids / box_off may be None: NULL, which n_boxes == 0 allows)
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        off = None if box_off is None else np.ascontiguousarray(box_off, dtype=np.int64).reshape(-1)
+        n = 0 if ids is None else ids.size
+        if off is not None and ids is not None and off.size != n:
+            raise ValueError(f"{name}: {n} ids and {off.size} offsets")
+        cells = _LL(0)
+        self.call(name, iv, n, None if ids is None else ids.ctypes.data_as(C.c_void_p),
+                  C.c_void_p(int(ptr or 0) or None), None if off is None else off.ctypes.data_as(C.c_void_p),
+                  np.ascontiguousarray(stride, dtype=np.int64).reshape(3), int(ghost), *extra,
+                  C.c_void_p(int(stream) or None), C.byref(cells))
+        return cells.value
+
+    def put_boxes(self, iv, ids, ptr, box_off, stride, ghost, stream=0):
+        """omg_put_boxes: variable iv of the boxes `ids` (1-based global ids of
+        this rank, any levels) from the blocks at device address ptr: element
+        (i,j,k) of box q at ptr[box_off[q] + (i-1) + (j-1)*stride[1] +
+        (k-1)*stride[2]] (doubles); ghost = 1: with the six face-ghost layers.
+        Ordered on the hipStream_t `stream`.  Returns the cells copied."""
+        return self._boxes("put_boxes", iv, ids, ptr, box_off, stride, ghost, (), stream)
+
+    def get_boxes(self, iv, ids, ptr, box_off, stride, ghost, fill, stream=0):
+        """omg_get_boxes: the reverse copy; fill: the ghost cells of iv are
+        filled first on every level (collective on several ranks)."""
+        return self._boxes("get_boxes", iv, ids, ptr, box_off, stride, ghost, (int(bool(fill)),), stream)
 
     def scalar(self, name, *args):
         r = _D(0.0)

@@ -18,6 +18,7 @@ module m_omg_capi
   public :: omg_set_subtract_mean, omg_set_bc, omg_set_bc_faces
   public :: omg_level_size, omg_upload_level, omg_download_level
   public :: omg_put_dense, omg_get_dense, omg_get_dense_grad
+  public :: omg_put_boxes, omg_get_boxes
   public :: omg_fas_vcycle, omg_fas_fmg, omg_apply_op, omg_phi_bc_store
   public :: omg_synchronize, omg_diffusion_solve
   public :: omg_poisson_free_3d, omg_free_planes
@@ -206,6 +207,36 @@ module m_omg_capi
        type(c_ptr), value               :: stream, n_cells
        integer(c_int) :: ierr
      end function omg_get_dense_grad
+
+     ! omg_put_boxes / omg_get_boxes (include/omg.h): variable iv of the listed
+     ! boxes <-> blocks of a pool in device memory.  ids and box_off are host
+     ! arrays of n_boxes entries (unused when n_boxes = 0); dev, stream and
+     ! n_cells go by value as for omg_put_dense
+     function omg_put_boxes(ctx, iv, n_boxes, ids, dev, box_off, stride, ghost, stream, n_cells) &
+          bind(C, name="omg_put_boxes") result(ierr)
+       import :: c_ptr, c_int, c_long_long
+       type(c_ptr), value               :: ctx
+       integer(c_int), value            :: iv, n_boxes
+       integer(c_int), intent(in)       :: ids(*)
+       type(c_ptr), value               :: dev
+       integer(c_long_long), intent(in) :: box_off(*), stride(3)
+       integer(c_int), value            :: ghost
+       type(c_ptr), value               :: stream, n_cells
+       integer(c_int) :: ierr
+     end function omg_put_boxes
+
+     function omg_get_boxes(ctx, iv, n_boxes, ids, dev, box_off, stride, ghost, fill, stream, n_cells) &
+          bind(C, name="omg_get_boxes") result(ierr)
+       import :: c_ptr, c_int, c_long_long
+       type(c_ptr), value               :: ctx
+       integer(c_int), value            :: iv, n_boxes
+       integer(c_int), intent(in)       :: ids(*)
+       type(c_ptr), value               :: dev
+       integer(c_long_long), intent(in) :: box_off(*), stride(3)
+       integer(c_int), value            :: ghost, fill
+       type(c_ptr), value               :: stream, n_cells
+       integer(c_int) :: ierr
+     end function omg_get_boxes
 
      function omg_fas_vcycle(ctx, highest_lvl, want_max_res, max_res, standalone) &
           bind(C, name="omg_fas_vcycle") result(ierr)

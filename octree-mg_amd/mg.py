@@ -220,6 +220,92 @@ class MG(MGTree):
                                         scale, fill, torch.cuda.current_stream(used[0].device).cuda_stream)
         return out, cells
 
+    def _blocks_args(self, t, ids, ghost_width, ghosts, what):
+        """The checks of set_blocks / get_blocks on a tensor [n, m, m, m], before
+        any call into the library; returns (ids, box_off, stride, nc)."""
+        import torch
+        ghost_width = int(ghost_width)
+        if ghost_width < 0:
+            raise ValueError(f"{what}: ghost_width {ghost_width} < 0")
+        if ghosts and ghost_width < 1:
+            raise ValueError(f"{what}: ghosts=True needs ghost_width >= 1")
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{what}: a torch tensor [box, k, j, i] is required")
+        if t.dtype != torch.float64:
+            raise ValueError(f"{what}: dtype {t.dtype}, torch.float64 is required")
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        n = int(t.shape[0])
+        if len(ids) != n:
+            raise ValueError(f"{what}: {len(ids)} ids for {n} blocks")
+        if n and (ids.min() < 1 or ids.max() > self.n_boxes):
+            raise ValueError(f"{what}: a box id outside 1..{self.n_boxes}")
+        sizes = {int(self.box_size_lvl[int(l)]) for l in np.unique(self.lvl[ids])} if n else set()
+        if len(sizes) > 1:
+            raise ValueError(f"{what}: the listed boxes have the box sizes {sorted(sizes)}, one is required")
+        m = int(t.shape[3])
+        nc = sizes.pop() if sizes else m - 2 * ghost_width
+        if tuple(t.shape[1:]) != (nc + 2 * ghost_width,) * 3:
+            raise ValueError(f"{what}: blocks of shape {tuple(t.shape[1:])}, box size {nc} with ghost_width "
+                             f"{ghost_width} needs {(nc + 2 * ghost_width,) * 3}")
+        sb, s2, s1, s0 = (int(v) for v in t.stride())
+        if n and m:
+            if s0 != 1:
+                raise ValueError(f"{what}: the last stride is {s0}, 1 is required")
+            if s1 < m or s2 < s1 * m or sb < 0:
+                raise ValueError(f"{what}: strides {tuple(t.stride())} of shape {tuple(t.shape)}: stride(2) >= m, "
+                                 "stride(1) >= stride(2) * m and stride(0) >= 0 are required")
+        if not t.is_cuda:
+            raise ValueError(f"{what}: the tensor is on {t.device}, not on the context's GPU")
+        self._require_alloc()
+        dev = self.ctx.device
+        if dev >= 0 and t.device.index != dev:
+            raise ValueError(f"{what}: the tensor is on {t.device}, the context on GPU {dev}")
+        box_off = np.arange(n, dtype=np.int64) * sb + ghost_width * (1 + s1 + s2)
+        return ids.astype(np.int32), box_off, (1, max(s1, 1), max(s2, 1)), nc
+
+    def set_blocks(self, iv, blocks, ids, ghost_width=0, ghosts=False):
+        """omg_put_boxes: variable iv of the boxes `ids` (1-based global ids of
+        this rank, in any order, on any levels that share one box size nc) from
+        `blocks`, a torch.float64 tensor [n, m, m, m] ([box, k, j, i]) on the
+        context's GPU with m = nc + 2 * ghost_width: the block pool of an AMR
+        code with ghost_width ghost layers of its own.  The last stride is 1,
+        stride(2) >= m, stride(1) >= stride(2) * m and the box stride is any
+        value >= 0: a slice pool[:, iw] of a pool [n, nw, m, m, m] is a valid
+        argument.  The interiors move; ghosts=True (ghost_width >= 1): also
+        the innermost ghost layer on the six faces, as set_level's ghosts.
+        Edges, corners and outer ghost layers are never read.  Ordered on
+        torch's current stream: no host synchronisation.  With several ranks
+        a put of phi is collective (a rank with nothing passes n = 0).
+        Returns the number of cells copied."""
+        import torch
+        ids, off, stride, _ = self._blocks_args(blocks, ids, ghost_width, ghosts, "set_blocks")
+        return self.ctx.put_boxes(iv, ids, blocks.data_ptr(), off, stride, int(bool(ghosts)),
+                                  torch.cuda.current_stream(blocks.device).cuda_stream)
+
+    def get_blocks(self, iv, ids, out=None, ghost_width=0, ghosts=False, fill=True):
+        """omg_get_boxes into `out` [n, m, m, m] (default: torch.empty of that
+        shape), laid out as set_blocks' tensor.  ghosts=True: with the
+        innermost ghost layer on the six faces; edges, corners and everything
+        else of `out` outside the copied cells keep their values.  fill: the
+        ghost cells of iv are filled first on every level (collective on
+        several ranks); without it they are used as they stand.  Returns
+        (out, cells copied)."""
+        import torch
+        if out is None:
+            self._require_alloc()
+            idl = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+            sizes = {int(self.box_size_lvl[int(l)]) for l in np.unique(self.lvl[idl])} if len(idl) else {0}
+            if len(sizes) > 1:
+                raise ValueError(f"get_blocks: the listed boxes have the box sizes {sorted(sizes)}, one is required")
+            m = sizes.pop() + 2 * int(ghost_width)
+            dev = self.ctx.device
+            out = torch.empty((len(idl), m, m, m), dtype=torch.float64,
+                              device=torch.device("cuda", dev if dev >= 0 else torch.cuda.current_device()))
+        ids, off, stride, _ = self._blocks_args(out, ids, ghost_width, ghosts, "get_blocks")
+        cells = self.ctx.get_boxes(iv, ids, out.data_ptr(), off, stride, int(bool(ghosts)), fill,
+                                   torch.cuda.current_stream(out.device).cuda_stream)
+        return out, cells
+
     def _require_alloc(self):
         if not self.is_allocated:
             raise RuntimeError("allocate_storage: tree is not allocated")
