@@ -53,473 +53,6 @@ double* stage(omg_ctx* c, size_t n) {
   return c->d_stage;
 }
 
-// --- dense device I/O (omg_put_dense / omg_get_dense, kernels: omg_dense.hip)
-constexpr long long kDenseMax = 1LL << 40;   // bound on |lo|, n and the strides (no overflow below)
-
-// The clip records of a window, from the level's cache or built now.  aligned:
-// the window's base is 16-B aligned; generic: the per-cell kernel for every
-// box; own_only: the host's own partition of a replicated level.
-DensePlan& dense_plan(omg_ctx* c, Level& L, const long long* lo, const long long* n, const long long* stride,
-                      bool aligned, bool generic, bool own_only) {
-  for (auto& P : L.dense)
-    if (std::equal(lo, lo + 3, P.lo) && std::equal(n, n + 3, P.n) && std::equal(stride, stride + 3, P.stride) &&
-        P.aligned == aligned && P.generic == generic && P.own_only == own_only) {
-      P.age = ++c->dense_age;
-      return P;
-    }
-  if ((int)L.dense.size() < kDensePlans) L.dense.emplace_back();
-  DensePlan& P = *std::min_element(L.dense.begin(), L.dense.end(),
-                                   [](const DensePlan& a, const DensePlan& b) { return a.age < b.age; });
-  // (the oldest window makes room: its records may still be on their way to
-  // the device or being read there; the only host wait of the dense entries)
-  if (P.d_clips) host_sync(c, c->stream);
-  std::copy(lo, lo + 3, P.lo);
-  std::copy(n, n + 3, P.n);
-  std::copy(stride, stride + 3, P.stride);
-  P.aligned = aligned;
-  P.generic = generic;
-  P.own_only = own_only;
-  P.age = ++c->dense_age;
-  P.n_row = P.n_gen = 0;
-  P.n_cells = 0;
-  std::vector<DenseClip> row, gen;
-  const long long nc = L.nc;
-  const bool row_ok = !generic && aligned && dense_row_nc(L.nc) && stride[1] % 2 == 0 && stride[2] % 2 == 0;
-  auto clip = [&](int b) {
-    DenseClip r{};
-    r.box = b;
-    int* lohi[3][2] = {{&r.i0, &r.i1}, {&r.j0, &r.j1}, {&r.k0, &r.k1}};
-    long long cells = 1;
-    for (int d = 0; d < 3; d++) {
-      const long long g0 = ((long long)c->ix[(size_t)(L.ids[b] - 1) * 3 + d] - 1) * nc;   // global index of local cell 1
-      const long long a = std::max(g0, lo[d]), e = std::min(g0 + nc, lo[d] + n[d]);
-      if (a >= e) return;
-      *lohi[d][0] = (int)(a - g0) + 1;
-      *lohi[d][1] = (int)(e - g0);
-      r.off += (a - lo[d]) * stride[d];
-      cells *= e - a;
-    }
-    P.n_cells += cells;
-    (row_ok && r.i0 == 1 && r.i1 == L.nc && r.off % 2 == 0 ? row : gen).push_back(r);
-  };
-  if (own_only)
-    for (int b : L.host_local) clip(b);
-  else
-    for (int b = 0; b < L.n; b++) clip(b);
-  P.n_row = (int)row.size();
-  P.n_gen = (int)gen.size();
-  row.insert(row.end(), gen.begin(), gen.end());
-  if (!c->host_only && !row.empty()) {
-    if (row.size() > P.cap) {
-      dfree(P.d_clips);
-      if (P.h_clips) HIPCHK(hipHostFree(P.h_clips));
-      P.h_clips = nullptr;
-      P.cap = 0;
-      HIPCHK(hipHostMalloc((void**)&P.h_clips, sizeof(DenseClip) * row.size()));
-      HIPCHK(hipMalloc(&P.d_clips, sizeof(DenseClip) * row.size()));
-      P.cap = row.size();
-    }
-    // from pinned memory, in stream order ahead of the kernel: no host wait
-    // (the pinned copy is rewritten only after the wait above)
-    std::copy(row.begin(), row.end(), P.h_clips);
-    HIPCHK(hipMemcpyAsync(P.d_clips, P.h_clips, sizeof(DenseClip) * row.size(), hipMemcpyHostToDevice, c->stream));
-  }
-  return P;
-}
-
-// The argument checks the dense entries share (before anything is launched):
-// level, variable and window; returns whether the window is empty.
-template <typename Fail>
-bool dense_check_window(omg_ctx* c, const Level* L, int iv, const long long* lo, const long long* n,
-                        const long long* stride, Fail&& fail) {
-  if (!L) fail("no such level");
-  if (iv < 1 || iv > c->n_vars) fail("bad variable index");
-  if (!lo || !n || !stride) fail("lo, n and stride are required");
-  for (int d = 0; d < 3; d++) {
-    if (n[d] < 0) fail("negative extent");
-    if (n[d] > kDenseMax || lo[d] > kDenseMax || lo[d] < -kDenseMax || stride[d] > kDenseMax)
-      fail("window out of range");
-  }
-  if (stride[0] != 1) fail("stride[0] must be 1");
-  const bool empty = n[0] == 0 || n[1] == 0 || n[2] == 0;
-  if (!empty) {
-    if (stride[1] < n[0]) fail("stride[1] < n[0]");
-    if (stride[2] / n[1] < stride[1]) fail("stride[2] < stride[1]*n[1]");
-    if (stride[2] > LLONG_MAX / 8 / n[2]) fail("window out of range");
-  }
-  return empty;
-}
-
-// doubles from a non-empty window's first element to one past its last
-long long dense_extent(const long long* n, const long long* stride) {
-  return (n[2] - 1) * stride[2] + (n[1] - 1) * stride[1] + n[0];
-}
-
-// the pointer must be device memory of this GPU, the window inside its allocation
-template <typename Fail>
-void dense_check_pointer(omg_ctx* c, const double* dev, const long long* n, const long long* stride, Fail&& fail) {
-  hipPointerAttribute_t at{};
-  if (hipPointerGetAttributes(&at, dev) != hipSuccess) {
-    (void)hipGetLastError();
-    fail("the pointer is not device memory");
-  }
-  if (at.type != hipMemoryTypeDevice) fail("the pointer is not device memory");
-  if (at.device != c->device) fail("the pointer belongs to another GPU than the context's");
-  hipDeviceptr_t base = nullptr;
-  size_t bytes = 0;
-  if (hipMemGetAddressRange(&base, &bytes, (hipDeviceptr_t)dev) == hipSuccess) {
-    if ((const char*)dev + (size_t)dense_extent(n, stride) * sizeof(double) > (const char*)base + bytes)
-      fail("the window reaches past the end of the pointer's allocation");
-  } else {
-    (void)hipGetLastError();
-  }
-}
-
-void dense_io(omg_ctx* c, int lvl, int iv, double* dev, const long long* lo, const long long* n,
-              const long long* stride, void* stream, long long* n_cells, bool put) {
-  const char* who = put ? "omg_put_dense" : "omg_get_dense";
-  auto fail = [&](const std::string& what) { throw OmgError(std::string(who) + ": " + what); };
-  Level* L = level_ptr(c, lvl);
-  const bool empty = dense_check_window(c, L, iv, lo, n, stride, fail);
-  if (!empty && !dev) fail("NULL pointer with a non-empty window");
-  if (put && L->replicated)
-    fail("level " + std::to_string(lvl) + " is replicated on every rank: use omg_upload_level");
-  const bool generic = env_flag("OMG_DENSE_GENERIC");
-  const bool aligned = ((uintptr_t)dev & 15) == 0;
-  if (c->host_only) {
-    if (n_cells) *n_cells = empty ? 0 : dense_plan(c, *L, lo, n, stride, aligned, generic, L->replicated).n_cells;
-    return;
-  }
-  if (!empty) dense_check_pointer(c, dev, n, stride, fail);
-  if (put) {
-    enter(c);
-    // (before the early return, as omg_upload_level)
-    if (iv == 1) phi_dirty(c, lvl);
-  } else {
-    enter(c, false);
-  }
-  if (n_cells) *n_cells = 0;
-  if (empty || !L->n) return;
-  DensePlan& P = dense_plan(c, *L, lo, n, stride, aligned, generic, L->replicated);
-  if (n_cells) *n_cells = P.n_cells;
-  if (!P.n_cells) return;
-  if ((long long)P.n_gen * 16 > INT_MAX) fail("too many boxes for one launch");
-  hipStream_t user = (hipStream_t)stream;
-  const bool foreign = user != c->stream;
-  if (foreign) {
-    HIPCHK(hipEventRecord(c->ev_dense_in, user));
-    HIPCHK(hipStreamWaitEvent(c->stream, c->ev_dense_in, 0));
-  }
-  {
-    Prof p(c, put ? "dense_put" : "dense_get", (double)P.n_cells, lvl);
-    const LevelView V = L->view();
-    if (P.n_row) {
-      Prof pr(c, put ? "dense_put_row" : "dense_get_row", (double)P.n_row * L->nc * L->nc * L->nc, lvl);
-      launch_dense_row(V, iv, P.d_clips, P.n_row, dev, stride[1], stride[2], put, c->stream);
-    }
-    launch_dense_cell(V, iv, P.d_clips + P.n_row, P.n_gen, dev, stride[1], stride[2], put, c->stream);
-    HIPCHK(hipGetLastError());
-  }
-  if (foreign) {
-    HIPCHK(hipEventRecord(c->ev_dense_out, c->stream));
-    HIPCHK(hipStreamWaitEvent(user, c->ev_dense_out, 0));
-  }
-}
-
-// omg_get_dense_grad (kernels: omg_dense_grad.hip): omg_get_dense's window,
-// clip records and stream ordering; up to three component windows.
-void dense_grad(omg_ctx* c, int lvl, int iv, double* const* dev, const long long* lo, const long long* n,
-                const long long* stride, double scale, bool fill, void* stream, long long* n_cells) {
-  auto fail = [&](const std::string& what) { throw OmgError("omg_get_dense_grad: " + what); };
-  Level* L = level_ptr(c, lvl);
-  const bool empty = dense_check_window(c, L, iv, lo, n, stride, fail);
-  if (!dev) fail("the array of component pointers is required");
-  bool aligned = true, any = false;
-  for (int d = 0; d < 3; d++)
-    if (dev[d]) {
-      any = true;
-      aligned = aligned && ((uintptr_t)dev[d] & 15) == 0;
-    }
-  if (!empty) {
-    if (!any) fail("NULL pointers for all three components with a non-empty window");
-    const uintptr_t bytes = (uintptr_t)dense_extent(n, stride) * sizeof(double);
-    for (int d = 0; d < 3; d++)
-      for (int e = d + 1; e < 3; e++)
-        if (dev[d] && dev[e] && (uintptr_t)dev[d] < (uintptr_t)dev[e] + bytes &&
-            (uintptr_t)dev[e] < (uintptr_t)dev[d] + bytes)
-          fail("the windows of components " + std::to_string(d) + " and " + std::to_string(e) + " overlap");
-  }
-  const bool generic = env_flag("OMG_DENSE_GENERIC");
-  if (c->host_only) {
-    if (n_cells) *n_cells = empty ? 0 : dense_plan(c, *L, lo, n, stride, aligned, generic, L->replicated).n_cells;
-    return;
-  }
-  if (!empty)
-    for (int d = 0; d < 3; d++)
-      if (dev[d]) dense_check_pointer(c, dev[d], n, stride, fail);
-  // a fill of another variable than phi writes its ghosts, as omg_fill_ghost_cells_lvl
-  enter(c, fill && iv != 1);
-  // (before the early returns: the fill is collective; phi's is skipped where
-  // it stands, a decision every rank makes alike)
-  if (fill && (iv != 1 || !L->phi_gc_ok)) fill_gc_lvl(c, lvl, iv);
-  if (n_cells) *n_cells = 0;
-  if (empty || !L->n) return;
-  DensePlan& P = dense_plan(c, *L, lo, n, stride, aligned, generic, L->replicated);
-  if (n_cells) *n_cells = P.n_cells;
-  if (!P.n_cells) return;
-  if ((long long)P.n_gen * 16 > INT_MAX) fail("too many boxes for one launch");
-  DenseGrad G;
-  for (int d = 0; d < 3; d++) {
-    G.out[d] = dev[d];
-    G.f[d] = (0.5 * scale) / L->dr[d];
-  }
-  hipStream_t user = (hipStream_t)stream;
-  const bool foreign = user != c->stream;
-  if (foreign) {
-    HIPCHK(hipEventRecord(c->ev_dense_in, user));
-    HIPCHK(hipStreamWaitEvent(c->stream, c->ev_dense_in, 0));
-  }
-  {
-    Prof p(c, "dense_grad", (double)P.n_cells, lvl);
-    const LevelView V = L->view();
-    if (P.n_row) {
-      Prof pr(c, "dense_grad_row", (double)P.n_row * L->nc * L->nc * L->nc, lvl);
-      launch_dense_grad_tile(V, iv, P.d_clips, P.n_row, G, stride[1], stride[2], c->stream);
-    }
-    launch_dense_grad_cell(V, iv, P.d_clips + P.n_row, P.n_gen, G, stride[1], stride[2], c->stream);
-    HIPCHK(hipGetLastError());
-  }
-  if (foreign) {
-    HIPCHK(hipEventRecord(c->ev_dense_out, c->stream));
-    HIPCHK(hipStreamWaitEvent(user, c->ev_dense_out, 0));
-  }
-}
-
-// --- device block I/O (omg_put_boxes / omg_get_boxes, kernels: omg_boxes.hip)
-// What tools/box_io_bench.py measured, in place of switches:
-// blocks that are not 16-B aligned take the tile kernel's 8-B variant, except
-// a get with ghosts, whose interior rows the shifted variant covers with
-// whole pairs (OMG_BOXES_ODD=8 / 16 overrides, for A/B timing).  The per-cell kernel
-// takes a level with fewer listed boxes than kBoxesTileMin (one workgroup per
-// box leaves the GPU short of work: it won at 512 and 960 boxes, the tile
-// kernel from 1728 on), and a get of interiors into rows with a gap between
-// them (stride[1] > nc) of more than kBoxesGapGetCells cells (it won at 8000
-// boxes of 16^3 and more, the tile kernel at 4096, whose pool the Infinity
-// Cache still holds).  OMG_BOXES_TILE=1: the tile kernel wherever it can serve.
-constexpr int kBoxesTileMin = 1536;
-constexpr long long kBoxesGapGetCells = 6144LL * 4096;
-
-bool boxes_odd8(bool put, int ghost) {
-  const char* v = getenv("OMG_BOXES_ODD");
-  if (v && !std::strcmp(v, "8")) return true;
-  if (v && !std::strcmp(v, "16")) return false;
-  return put || !ghost;
-}
-
-// The records of a list: every id checked (range, owner, replicated level,
-// listed once), grouped by level.  Touches nothing of the context.
-template <typename Fail>
-void boxes_build(omg_ctx* c, BoxPlan& P, int n_boxes, const int* ids, const long long* box_off, bool put,
-                 Fail&& fail) {
-  P.ids.assign(ids, ids + n_boxes);
-  P.off.assign(box_off, box_off + n_boxes);
-  P.recs.resize(n_boxes);
-  std::map<int, int> per_lvl;   // level -> boxes listed
-  std::vector<int> sorted(ids, ids + n_boxes);
-  std::sort(sorted.begin(), sorted.end());
-  for (int q = 0; q < n_boxes; q++) {
-    const int id = sorted[q];
-    if (id < 1 || id > c->n_boxes) fail("box id " + std::to_string(id) + " is out of range");
-    if (q && sorted[q - 1] == id) fail("box id " + std::to_string(id) + " is listed twice");
-  }
-  for (int q = 0; q < n_boxes; q++) {
-    const int id = ids[q], lvl = c->lvl[id - 1];
-    const Level* L = level_ptr(c, lvl);
-    if (!L || c->local_index[id] < 0) fail("box id " + std::to_string(id) + " is not owned by this rank");
-    if (L->replicated) {
-      if (put) fail("level " + std::to_string(lvl) + " is replicated on every rank: use omg_upload_level");
-      if (c->rank_of[id - 1] != c->rank)
-        fail("box id " + std::to_string(id) + " on the replicated level " + std::to_string(lvl) +
-             " is not one of this rank's own boxes");
-      P.any_replicated = true;
-    }
-    if (box_off[q] > kDenseMax || box_off[q] < -kDenseMax) fail("box_off out of range");
-    per_lvl[lvl]++;
-  }
-  int first = 0;
-  for (auto& kv : per_lvl) {
-    const Level* L = level_ptr(c, kv.first);
-    BoxGroup G;
-    G.lvl = kv.first;
-    G.first = first;
-    G.n = 0;
-    P.groups.push_back(G);
-    first += kv.second;
-    P.nc_max = std::max(P.nc_max, L->nc);
-  }
-  bool have_ext = false;
-  for (int q = 0; q < n_boxes; q++) {
-    const int id = ids[q], lvl = c->lvl[id - 1];
-    const Level* L = level_ptr(c, lvl);
-    BoxGroup& G = *std::find_if(P.groups.begin(), P.groups.end(), [&](const BoxGroup& g) { return g.lvl == lvl; });
-    P.recs[G.first + G.n++] = BoxRec{c->local_index[id], lvl, box_off[q]};
-    if (!P.aligned || (box_off[q] | P.stride[1] | P.stride[2]) & 1) G.odd = true;
-    const long long nc = L->nc;
-    P.n_cells += nc * nc * nc + (long long)P.ghost * 6 * nc * nc;
-    // first and last touched element: (1,1,0) and (nc,nc,nc+1) with ghosts
-    const long long lo = box_off[q] - (P.ghost ? P.stride[2] : 0);
-    const long long hi = box_off[q] + (nc - 1) + (nc - 1) * P.stride[1] + (nc - 1 + P.ghost) * P.stride[2];
-    P.lo_ext = have_ext ? std::min(P.lo_ext, lo) : lo;
-    P.hi_ext = have_ext ? std::max(P.hi_ext, hi) : hi;
-    have_ext = true;
-  }
-}
-
-void box_io(omg_ctx* c, int iv, int n_boxes, const int* ids, double* dev, const long long* box_off,
-            const long long* stride, int ghost, bool fill, void* stream, long long* n_cells, bool put) {
-  const char* who = put ? "omg_put_boxes" : "omg_get_boxes";
-  auto fail = [&](const std::string& what) { throw OmgError(std::string(who) + ": " + what); };
-  if (iv < 1 || iv > c->n_vars) fail("bad variable index");
-  if (ghost != 0 && ghost != 1) fail("ghost must be 0 or 1");
-  if (n_boxes < 0) fail("negative n_boxes");
-  if (!stride) fail("stride is required");
-  if (stride[0] != 1) fail("stride[0] must be 1");
-  if (stride[1] < 1 || stride[2] < 1 || stride[1] > kDenseMax || stride[2] > kDenseMax) fail("stride out of range");
-  if (n_boxes > 0 && (!ids || !box_off)) fail("NULL ids or box_off with n_boxes > 0");
-  if (n_boxes > 0 && !dev) fail("NULL pointer with n_boxes > 0");
-  if (c->levels.empty()) fail("no tree (omg_tree_setup)");
-  // (the switches choose the kernel at launch: the records do not depend on them)
-  const bool generic = env_flag("OMG_BOXES_GENERIC"), force_tile = env_flag("OMG_BOXES_TILE");
-  const bool odd8 = boxes_odd8(put, ghost);
-  const bool aligned = ((uintptr_t)dev & 15) == 0;
-  // a cached list was checked when it was built
-  BoxPlan* P = nullptr;
-  for (auto& Q : c->box_plans)
-    if ((int)Q.ids.size() == n_boxes && Q.ghost == ghost && std::equal(stride, stride + 3, Q.stride) &&
-        Q.aligned == aligned && std::equal(ids, ids + n_boxes, Q.ids.begin()) &&
-        std::equal(box_off, box_off + n_boxes, Q.off.begin()))
-      P = &Q;
-  BoxPlan fresh;
-  if (P) {
-    if (put && P->any_replicated) {
-      for (int q = 0; q < n_boxes; q++)
-        if (level_ptr(c, c->lvl[ids[q] - 1])->replicated)
-          fail("level " + std::to_string(c->lvl[ids[q] - 1]) + " is replicated on every rank: use omg_upload_level");
-    }
-  } else {
-    fresh.ghost = ghost;
-    std::copy(stride, stride + 3, fresh.stride);
-    fresh.aligned = aligned;
-    boxes_build(c, fresh, n_boxes, ids, box_off, put, fail);
-  }
-  const BoxPlan& R = P ? *P : fresh;
-  if (n_boxes > 0) {
-    const long long m = R.nc_max + 2 * ghost;
-    if (stride[1] < m) fail("stride[1] < nc + 2*ghost");
-    if (stride[2] / m < stride[1]) fail("stride[2] < stride[1]*(nc + 2*ghost)");
-  }
-  if (c->host_only) {
-    if (n_cells) *n_cells = R.n_cells;
-    return;
-  }
-  if (n_boxes > 0) {
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, dev) != hipSuccess) {
-      (void)hipGetLastError();
-      fail("the pointer is not device memory");
-    }
-    if (at.type != hipMemoryTypeDevice) fail("the pointer is not device memory");
-    if (at.device != c->device) fail("the pointer belongs to another GPU than the context's");
-    hipDeviceptr_t base = nullptr;
-    size_t bytes = 0;
-    if (hipMemGetAddressRange(&base, &bytes, (hipDeviceptr_t)dev) == hipSuccess) {
-      // (in doubles from the allocation's base: |offsets| <= 20 * 2^40)
-      const long long d0 = (long long)(((const char*)dev - (const char*)base) / 8);
-      const long long rem = ((const char*)dev - (const char*)base) % 8;
-      if (d0 + R.lo_ext < 0) fail("a block starts before the pointer's allocation");
-      if ((unsigned long long)(d0 + R.hi_ext + 1) * 8 + (unsigned long long)rem > bytes)
-        fail("a block reaches past the end of the pointer's allocation");
-    } else {
-      (void)hipGetLastError();
-    }
-    for (const BoxGroup& G : R.groups)
-      if ((long long)G.n * 16 > INT_MAX) fail("too many boxes for one launch");
-  }
-  // --- nothing of the state was touched up to here
-  if (put) {
-    enter(c);
-    // (every level: a rank cannot know which levels its peers list, and the
-    // stand-alone fill decision must fall alike on every rank)
-    if (iv == 1) phi_dirty_all(c);
-  } else {
-    // a fill of another variable than phi writes its ghosts, as omg_fill_ghost_cells
-    enter(c, fill && iv != 1);
-    if (fill)
-      for (int l = c->lowest; l <= c->highest; l++) {
-        const Level* L = level_ptr(c, l);
-        if (iv != 1 || !L || !L->phi_gc_ok) fill_gc_lvl(c, l, iv);
-      }
-  }
-  if (n_cells) *n_cells = R.n_cells;
-  if (n_boxes == 0) return;
-  if (!P) {
-    if ((int)c->box_plans.size() < kBoxPlans) c->box_plans.emplace_back();
-    BoxPlan& S = *std::min_element(c->box_plans.begin(), c->box_plans.end(),
-                                   [](const BoxPlan& a, const BoxPlan& b) { return a.age < b.age; });
-    // (the oldest list makes room: its records may still be on their way to
-    // the device or being read there; the only host wait of these entries)
-    if (S.d_recs) host_sync(c, c->stream);
-    fresh.h_recs = S.h_recs;
-    fresh.d_recs = S.d_recs;
-    fresh.cap = S.cap;
-    S = std::move(fresh);
-    if (S.recs.size() > S.cap) {
-      dfree(S.d_recs);
-      if (S.h_recs) HIPCHK(hipHostFree(S.h_recs));
-      S.h_recs = nullptr;
-      S.cap = 0;
-      HIPCHK(hipHostMalloc((void**)&S.h_recs, sizeof(BoxRec) * S.recs.size()));
-      HIPCHK(hipMalloc(&S.d_recs, sizeof(BoxRec) * S.recs.size()));
-      S.cap = S.recs.size();
-    }
-    // from pinned memory, in stream order ahead of the kernels: no host wait
-    std::copy(S.recs.begin(), S.recs.end(), S.h_recs);
-    HIPCHK(hipMemcpyAsync(S.d_recs, S.h_recs, sizeof(BoxRec) * S.recs.size(), hipMemcpyHostToDevice, c->stream));
-    P = &S;
-  }
-  P->age = ++c->dense_age;
-  hipStream_t user = (hipStream_t)stream;
-  const bool foreign = user != c->stream;
-  if (foreign) {
-    HIPCHK(hipEventRecord(c->ev_dense_in, user));
-    HIPCHK(hipStreamWaitEvent(c->stream, c->ev_dense_in, 0));
-  }
-  {
-    Prof p(c, put ? "boxes_put" : "boxes_get", (double)P->n_cells);
-    for (const BoxGroup& G : P->groups) {
-      const Level* L = level_ptr(c, G.lvl);
-      const LevelView V = L->view();
-      const double cells = (double)G.n * ((double)L->nc * L->nc * L->nc + ghost * 6.0 * L->nc * L->nc);
-      const bool tile = !generic && boxes_tile_nc(L->nc) &&
-                        (force_tile || (G.n >= kBoxesTileMin && (put || ghost || stride[1] == L->nc ||
-                                                                 (long long)G.n * L->nc * L->nc * L->nc <=
-                                                                     kBoxesGapGetCells)));
-      if (tile) {
-        Prof pr(c, put ? "boxes_put_tile" : "boxes_get_tile", cells, G.lvl);
-        launch_boxes_tile(V, iv, P->d_recs + G.first, G.n, dev, stride[1], stride[2], ghost, put, odd8 && G.odd,
-                          c->stream);
-      } else {
-        launch_boxes_cell(V, iv, P->d_recs + G.first, G.n, dev, stride[1], stride[2], ghost, put, c->stream);
-      }
-    }
-    HIPCHK(hipGetLastError());
-  }
-  if (foreign) {
-    HIPCHK(hipEventRecord(c->ev_dense_out, c->stream));
-    HIPCHK(hipStreamWaitEvent(user, c->ev_dense_out, 0));
-  }
-}
-
 }  // namespace
 
 // ===========================================================================

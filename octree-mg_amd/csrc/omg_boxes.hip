@@ -41,8 +41,6 @@
 #include "omg_device.h"
 #include "omg_kernels.h"
 
-#include <algorithm>
-
 namespace omg {
 
 typedef double d2 __attribute__((ext_vector_type(2)));
@@ -207,7 +205,7 @@ void launch_boxes_tile(const LevelView& L, int iv, const BoxRec* recs, int n, do
 
 int boxes_cell_bpc(int nc, int ghost) {
   const long long m = nc + 2 * ghost;
-  return (int)std::min<long long>(std::max<long long>((m * m * m + 255) / 256, 1), 16);
+  return cell_bpc(m * m * m);
 }
 
 void launch_boxes_cell(const LevelView& L, int iv, const BoxRec* recs, int n, double* dev, long long s1,

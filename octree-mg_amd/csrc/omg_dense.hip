@@ -1,7 +1,7 @@
 // omg_dense.hip — dense device I/O (omg_put_dense / omg_get_dense): the
 // interior cells of a level's boxes <-> a dense window [z][y][x] of the
 // level's cell grid in the caller's device memory.  Ghost slots are never
-// touched.  The host (omg_api.cpp) clips every box against the window into a
+// touched.  The host (omg_devio.cpp) clips every box against the window into a
 // DenseClip record; the row kernel serves the boxes whose covered rows are
 // whole in x and 16-B aligned in the window, the per-cell kernel the others.
 //
@@ -17,8 +17,6 @@
 // Plain accesses: non-temporal ones on either side measured slower.
 #include "omg_device.h"
 #include "omg_kernels.h"
-
-#include <algorithm>
 
 namespace omg {
 
@@ -116,8 +114,7 @@ void launch_dense_row(const LevelView& L, int iv, const DenseClip* clips, int n,
 void launch_dense_cell(const LevelView& L, int iv, const DenseClip* clips, int n, double* dense, long long s1,
                        long long s2, bool put, hipStream_t st) {
   if (n <= 0) return;
-  const long long nc3 = (long long)L.nc * L.nc * L.nc;
-  const int bpc = (int)std::min<long long>(std::max<long long>((nc3 + 255) / 256, 1), 16);
+  const int bpc = cell_bpc((long long)L.nc * L.nc * L.nc);
   const unsigned grid = (unsigned)((long long)n * bpc);
   if (put) k_dense_cell<true><<<grid, 256, 0, st>>>(L, iv, clips, bpc, dense, s1, s2);
   else k_dense_cell<false><<<grid, 256, 0, st>>>(L, iv, clips, bpc, dense, s1, s2);

@@ -26,8 +26,6 @@
 #include "omg_device.h"
 #include "omg_kernels.h"
 
-#include <algorithm>
-
 namespace omg {
 
 typedef double d2 __attribute__((ext_vector_type(2)));
@@ -179,8 +177,7 @@ void launch_dense_grad_tile(const LevelView& L, int iv, const DenseClip* clips, 
 void launch_dense_grad_cell(const LevelView& L, int iv, const DenseClip* clips, int n, const DenseGrad& G,
                             long long s1, long long s2, hipStream_t st) {
   if (n <= 0) return;
-  const long long nc3 = (long long)L.nc * L.nc * L.nc;
-  const int bpc = (int)std::min<long long>(std::max<long long>((nc3 + 255) / 256, 1), 16);
+  const int bpc = cell_bpc((long long)L.nc * L.nc * L.nc);
   const unsigned grid = (unsigned)((long long)n * bpc);
   k_dense_grad_cell<<<grid, 256, 0, st>>>(L, iv, clips, bpc, G, s1, s2);
 }

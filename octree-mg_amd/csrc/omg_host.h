@@ -297,6 +297,14 @@ void enter(omg_ctx* c, bool writes = true);
 enum { kPlain = 0, kInCycle = 1 };
 void subtract_mean(omg_ctx* c, int iv, int ghosts, int mode = kPlain);
 
+// --- omg_devio.cpp
+void dense_io(omg_ctx* c, int lvl, int iv, double* dev, const long long* lo, const long long* n,
+              const long long* stride, void* stream, long long* n_cells, bool put);
+void dense_grad(omg_ctx* c, int lvl, int iv, double* const* dev, const long long* lo, const long long* n,
+                const long long* stride, double scale, bool fill, void* stream, long long* n_cells);
+void box_io(omg_ctx* c, int iv, int n_boxes, const int* ids, double* dev, const long long* box_off,
+            const long long* stride, int ghost, bool fill, void* stream, long long* n_cells, bool put);
+
 // --- omg_free_host.cpp
 void free_state_destroy(omg_ctx* c);
 double poisson_free_3d(omg_ctx* c, bool new_rhs, double max_fft_frac, bool fmgcycle, bool want_max_res,

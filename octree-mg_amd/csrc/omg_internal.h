@@ -146,14 +146,29 @@ struct DenseGrad {
   double f[3];
 };
 
+// The records of a cached plan (omg_devio.cpp): upload() grows both sides when
+// they are too small and copies the records in the order of the context
+// stream; release() is called by free_levels (no destructor calls HIP).
+template <typename T>
+struct RecordBuf {
+  T* h = nullptr;    // pinned: the source of the stream-ordered upload
+  T* d = nullptr;
+  size_t cap = 0;    // records h and d hold
+  void upload(omg_ctx* c, const std::vector<T>& recs);
+  void release() {
+    if (d) (void)hipFree(d);
+    if (h) (void)hipHostFree(h);
+    h = d = nullptr;
+    cap = 0;
+  }
+};
+
 // The records of one window, cached on the level: the boxes the row kernel
 // serves first (n_row), then those of the per-cell kernel (n_gen).
 struct DensePlan {
   long long lo[3] = {0, 0, 0}, n[3] = {0, 0, 0}, stride[3] = {0, 0, 0};
   bool aligned = false, generic = false, own_only = false;   // (part of the key)
-  DenseClip* h_clips = nullptr;     // pinned: the source of the stream-ordered upload
-  DenseClip* d_clips = nullptr;
-  size_t cap = 0;                   // records h_clips and d_clips hold
+  RecordBuf<DenseClip> buf;
   int n_row = 0, n_gen = 0;
   long long n_cells = 0;
   long long age = 0;                // last use (the oldest entry is replaced)
@@ -183,14 +198,12 @@ struct BoxPlan {
   long long stride[3] = {0, 0, 0};
   int ghost = 0;
   bool aligned = false;
-  std::vector<BoxRec> recs;         // (grouped; uploaded through h_recs)
+  std::vector<BoxRec> recs;         // (grouped; uploaded through buf)
   std::vector<BoxGroup> groups;
   bool any_replicated = false;      // some box lies on a replicated level (a put is refused)
   int nc_max = 0;
   long long lo_ext = 0, hi_ext = 0; // first and last touched element, relative to the base
-  BoxRec* h_recs = nullptr;         // pinned: the source of the stream-ordered upload
-  BoxRec* d_recs = nullptr;
-  size_t cap = 0;
+  RecordBuf<BoxRec> buf;
   long long n_cells = 0;
   long long age = 0;
 };

@@ -1,6 +1,8 @@
 // omg_kernels.h — launchers of the level kernels (omg_kernels.hip, omg_sweep.hip).
 #pragma once
 
+#include <algorithm>
+
 #include "omg_internal.h"
 
 namespace omg {
@@ -181,6 +183,10 @@ void launch_copy_var(const LevelView& L, int src, int dst, hipStream_t st);
 void launch_from_ref(const LevelView& L, int iv, const double* ref, hipStream_t st);
 void launch_to_ref(const LevelView& L, int iv, double* ref, double unstored, hipStream_t st);
 void launch_poison_ghosts(const LevelView& L, int n_vars, double poison, hipStream_t st);
+// workgroups (of 256 threads) per record of the per-cell device I/O kernels
+inline int cell_bpc(long long cells) {
+  return (int)std::min<long long>(std::max<long long>((cells + 255) / 256, 1), 16);
+}
 // dense device I/O (omg_dense.hip): variable iv's interior cells <-> a dense
 // window [z][y][x] (strides 1, s1, s2 doubles) by clip records (DenseClip);
 // the row kernel takes boxes of dense_row_nc() sizes whose covered rows are

@@ -188,10 +188,7 @@ void ensure_rhs_lex(omg_ctx* c) {
 // 16-69, m_prolong.f90:16-48).
 void free_levels(omg_ctx* c) {
   free_state_destroy(c);   // the FFT level belongs to the old tree
-  for (auto& P : c->box_plans) {   // (the lists name boxes of the old tree)
-    dfree(P.d_recs);
-    if (P.h_recs) (void)hipHostFree(P.h_recs);
-  }
+  for (auto& P : c->box_plans) P.buf.release();   // (the lists name boxes of the old tree)
   c->box_plans.clear();
   for (auto& kv : c->levels) {
     Level& L = kv.second;
@@ -206,10 +203,7 @@ void free_levels(omg_ctx* c) {
     dfree(L.d_galt);
     dfree(L.d_phi_buf); dfree(L.d_b3); dfree(L.d_b3c); L.n_b3 = 0; L.h_b3.clear();
     dfree(L.d_physbox);
-    for (auto& P : L.dense) {
-      dfree(P.d_clips);
-      if (P.h_clips) (void)hipHostFree(P.h_clips);
-    }
+    for (auto& P : L.dense) P.buf.release();
     L.dense.clear();
     dfree(L.d_rbsend); dfree(L.d_rbrecv); dfree(L.d_bnd); dfree(L.d_int); dfree(L.d_push0); dfree(L.d_bndface);
     for (Transfer* T : {&L.halo, &L.restr, &L.prol, &L.rbx, &L.repl, &L.deep_phi, &L.deep_rhs}) {

@@ -102,23 +102,26 @@ def _top_ids(tree):
 
 
 # (every tree's finest boxes hold 8^3 cells: m = 8 + 2*ghost)
+# (the change, the message after "omg_put_boxes: " / "omg_get_boxes: "; {id}: the id put first in the list)
 BAD = {
-    "stride0": dict(stride=(2, 8, 64)),
-    "stride1": dict(stride=(1, 7, 64)),
-    "stride1-ghost": dict(ghost=1, stride=(1, 9, 100), good=dict(ghost=1, stride=(1, 10, 100))),
-    "stride2": dict(stride=(1, 8, 63)),
-    "stride2-ghost": dict(ghost=1, stride=(1, 10, 99), good=dict(ghost=1, stride=(1, 10, 100))),
-    "ghost2": dict(ghost=2),
-    "ghost-1": dict(ghost=-1),
-    "iv0": dict(iv=0),
-    "iv_past": dict(iv=6),           # (the contexts hold n_vars = 5)
-    "id0": dict(first=0),
-    "id_past": dict(first="past"),
-    "twice": dict(first="second"),
-    "null_ids": dict(ids=None),
-    "null_off": dict(off=None),
-    "null_dev": dict(ptr=0),
-    "negative": dict(n=-1),
+    "stride0": (dict(stride=(2, 8, 64)), "stride[0] must be 1"),
+    "stride1": (dict(stride=(1, 7, 64)), "stride[1] < nc + 2*ghost"),
+    "stride1-ghost": (dict(ghost=1, stride=(1, 9, 100), good=dict(ghost=1, stride=(1, 10, 100))),
+                      "stride[1] < nc + 2*ghost"),
+    "stride2": (dict(stride=(1, 8, 63)), "stride[2] < stride[1]*(nc + 2*ghost)"),
+    "stride2-ghost": (dict(ghost=1, stride=(1, 10, 99), good=dict(ghost=1, stride=(1, 10, 100))),
+                      "stride[2] < stride[1]*(nc + 2*ghost)"),
+    "ghost2": (dict(ghost=2), "ghost must be 0 or 1"),
+    "ghost-1": (dict(ghost=-1), "ghost must be 0 or 1"),
+    "iv0": (dict(iv=0), "bad variable index"),
+    "iv_past": (dict(iv=6), "bad variable index"),           # (the contexts hold n_vars = 5)
+    "id0": (dict(first=0), "box id {id} is out of range"),
+    "id_past": (dict(first="past"), "box id {id} is out of range"),
+    "twice": (dict(first="second"), "box id {id} is listed twice"),
+    "null_ids": (dict(ids=None), "NULL ids or box_off with n_boxes > 0"),
+    "null_off": (dict(off=None), "NULL ids or box_off with n_boxes > 0"),
+    "null_dev": (dict(ptr=0), "NULL pointer with n_boxes > 0"),
+    "negative": (dict(n=-1), "negative n_boxes"),
 }
 
 
@@ -140,7 +143,7 @@ def test_bad_arguments_are_errors(ranks, bad, get):
     tree, ctx = ranks[0]
     ids = _top_ids(tree)
     assert len(ids) >= 2 and tree.box_size_lvl[tree.highest_lvl] == 8
-    b = dict(BAD[bad])
+    b, text = dict(BAD[bad][0]), BAD[bad][1]
     good = dict(iv=2, n=len(ids), ids=ids, ptr=PTR, off=[q * 1000 + 111 for q in range(len(ids))],
                 stride=(1, 8, 64), ghost=0)
     good.update(b.pop("good", {}))
@@ -153,7 +156,7 @@ def test_bad_arguments_are_errors(ranks, bad, get):
     a.update(b)
     with pytest.raises(omg.device.OmgError) as ex:
         _call(ctx, a, get)
-    assert ("omg_get_boxes" if get else "omg_put_boxes") in str(ex.value)
+    assert str(ex.value) == ("omg_get_boxes: " if get else "omg_put_boxes: ") + text.format(id=(a["ids"] or [0])[0])
     assert omg.device.lib().omg_last_error().decode() == str(ex.value)
     assert _call(ctx, good, get) == want   # (the context is as it was)
 

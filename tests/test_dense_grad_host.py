@@ -86,16 +86,17 @@ def test_strided_unaligned_and_empty_windows_count_alike(ranks):
     assert ctx.get_dense_grad(1, 2, (0, 0, 0), lo, (n[0], 0, n[2]), (1, n[0], 0)) == 0
 
 
+# (the change, the message after "omg_get_dense_grad: ")
 BAD = {
-    "no_level": dict(lvl=99),
-    "iv0": dict(iv=0),
-    "iv_past": dict(iv=6),           # (the contexts hold n_vars = 5)
-    "negative": dict(n=(8, -1, 8)),
-    "stride0": dict(stride=(2, 8, 64)),
-    "stride1": dict(stride=(1, 7, 64)),
-    "stride2": dict(stride=(1, 8, 63)),
-    "all_null": dict(ptrs=(0, 0, 0)),
-    "overlap": dict(ptrs=(PTRS[0], PTRS[0] + 8 * 511, 0)),
+    "no_level": (dict(lvl=99), "no such level"),
+    "iv0": (dict(iv=0), "bad variable index"),
+    "iv_past": (dict(iv=6), "bad variable index"),           # (the contexts hold n_vars = 5)
+    "negative": (dict(n=(8, -1, 8)), "negative extent"),
+    "stride0": (dict(stride=(2, 8, 64)), "stride[0] must be 1"),
+    "stride1": (dict(stride=(1, 7, 64)), "stride[1] < n[0]"),
+    "stride2": (dict(stride=(1, 8, 63)), "stride[2] < stride[1]*n[1]"),
+    "all_null": (dict(ptrs=(0, 0, 0)), "NULL pointers for all three components with a non-empty window"),
+    "overlap": (dict(ptrs=(PTRS[0], PTRS[0] + 8 * 511, 0)), "the windows of components 0 and 1 overlap"),
 }
 
 
@@ -105,10 +106,11 @@ def test_bad_arguments_are_errors(ranks, bad):
     a = dict(lvl=1, iv=2, ptrs=PTRS, lo=(0, 0, 0), n=(8, 8, 8), stride=(1, 8, 64))
     call = lambda: ctx.get_dense_grad(a["lvl"], a["iv"], a["ptrs"], a["lo"], a["n"], a["stride"])  # noqa: E731
     assert call() == 512
-    a.update(BAD[bad])
+    change, text = BAD[bad]
+    a.update(change)
     with pytest.raises(omg.device.OmgError) as ex:
         call()
-    assert "omg_get_dense_grad" in str(ex.value)
+    assert str(ex.value) == "omg_get_dense_grad: " + text
     assert omg.device.lib().omg_last_error().decode() == str(ex.value)
     a.update(dict(lvl=1, iv=2, ptrs=(PTRS[0], PTRS[0] + 8 * 512, 0), n=(8, 8, 8), stride=(1, 8, 64)))
     assert call() == 512   # (the context stays usable; windows that only touch do not overlap)

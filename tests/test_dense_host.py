@@ -68,15 +68,44 @@ def test_strided_and_empty_windows_count_alike(ranks):
     assert ctx.get_dense(1, 2, 0, lo, (n[0], 0, n[2]), (1, n[0], 0)) == 0   # (empty: NULL is fine)
 
 
+# (the change, the message after "omg_put_dense: " / "omg_get_dense: ")
+def test_six_windows_through_four_slots_are_each_counted_afresh(ranks):
+    """The level keeps the clipping of four windows, which omg_get_dense and
+    omg_get_dense_grad share: six windows in turn and the first again, through
+    the two entries alternately.  A slot that is reused is rebuilt completely."""
+    tree0 = ranks[0][0]
+    hi = tree0.highest_lvl
+    assert tree0.box_size_lvl[hi] == 8
+    # six windows inside the bounding box of the level's boxes, each smaller than the one before
+    org = np.array([U.box_origin(tree0, hi, i) for i in tree0.lvls[hi].ids])
+    b0, b1 = org.min(axis=0), org.max(axis=0) + 8
+    wins = [(tuple(int(v) for v in b0 + (q, 0, q // 2)), tuple(int(v) for v in b1 - b0 - (2 * q, q, q)))
+            for q in range(6)]
+    wins.append(wins[0])
+    totals = []
+    for tree, ctx in ranks:
+        want = [U.count_cells(tree, hi, lo, n, tree.lvls[hi].my_ids) for lo, n in wins]
+        got = []
+        for q, (lo, n) in enumerate(wins):
+            if q % 2:
+                got.append(ctx.get_dense_grad(hi, 1, (1 << 40, 2 << 40, 3 << 40), lo, n, U.contiguous(n)))
+            else:
+                got.append(ctx.get_dense(hi, 2, PTR, lo, n, U.contiguous(n)))
+        assert got == want
+        totals.append(want)
+    # (the windows differ in what they cover, so a count left over from the slot's last window would show)
+    assert len({sum(t[q] for t in totals) for q in range(6)}) == 6
+
+
 BAD = {
-    "stride0": dict(stride=(2, 8, 64)),
-    "stride1": dict(stride=(1, 7, 64)),
-    "stride2": dict(stride=(1, 8, 63)),
-    "negative": dict(n=(8, -1, 8)),
-    "iv0": dict(iv=0),
-    "iv_past": dict(iv=6),           # (the contexts hold n_vars = 5)
-    "no_level": dict(lvl=99),
-    "null": dict(ptr=0),
+    "stride0": (dict(stride=(2, 8, 64)), "stride[0] must be 1"),
+    "stride1": (dict(stride=(1, 7, 64)), "stride[1] < n[0]"),
+    "stride2": (dict(stride=(1, 8, 63)), "stride[2] < stride[1]*n[1]"),
+    "negative": (dict(n=(8, -1, 8)), "negative extent"),
+    "iv0": (dict(iv=0), "bad variable index"),
+    "iv_past": (dict(iv=6), "bad variable index"),           # (the contexts hold n_vars = 5)
+    "no_level": (dict(lvl=99), "no such level"),
+    "null": (dict(ptr=0), "NULL pointer with a non-empty window"),
 }
 
 
@@ -87,10 +116,11 @@ def test_bad_arguments_are_errors(ranks, bad, get):
     a = dict(lvl=1, iv=2, ptr=PTR, lo=(0, 0, 0), n=(8, 8, 8), stride=(1, 8, 64))
     f = ctx.get_dense if get else ctx.put_dense
     assert f(a["lvl"], a["iv"], a["ptr"], a["lo"], a["n"], a["stride"]) == 512
-    a.update(BAD[bad])
+    change, text = BAD[bad]
+    a.update(change)
     with pytest.raises(omg.device.OmgError) as ex:
         f(a["lvl"], a["iv"], a["ptr"], a["lo"], a["n"], a["stride"])
-    assert ("omg_get_dense" if get else "omg_put_dense") in str(ex.value)
+    assert str(ex.value) == ("omg_get_dense: " if get else "omg_put_dense: ") + text
     assert omg.device.lib().omg_last_error().decode() == str(ex.value)
 
 

@@ -251,6 +251,28 @@ def test_cut_windows_of_every_tree_level(monkeypatch):
                 assert np.array_equal(_bits(out), want), (lvl, lo, n, generic)
 
 
+def test_a_fifth_window_replaces_the_oldest(monkeypatch):
+    """The gradient shares omg_get_dense's four cached windows of a level: more
+    of them still give the right values, and only a call that replaces a
+    window whose records are on the device waits on the host."""
+    _switch(monkeypatch, False)
+    be = _backend(WIN16, profile=False)
+    mg, ctx, tree = be.mg, be.mg.ctx, be.tree
+    ids = tree.lvls[1].my_ids
+    mg.set_level(1, IPHI, _random_boxes(np.random.default_rng(43), len(ids), 16))
+    omg.mg_fill_ghost_cells_lvl(mg, 1, IPHI)
+    want = numpy_grad(tree, 1, ids, mg.get_level(1, IPHI), -1.0)
+    ctx.call("synchronize")
+    waits = []
+    for z in (0, 2, 4, 6, 8, 0):   # (five distinct windows; the first was replaced by then)
+        before = ctx.host_sync_count()
+        out, cells = mg.get_dense_grad(1, IPHI, lo=(0, 0, z), shape=(16, 32, 32), scale=-1.0)
+        waits.append(ctx.host_sync_count() - before)
+        assert cells == 16 * 32 * 32
+        assert np.array_equal(_bits(out), _crop(want, (0, 0, z), (32, 32, 16))), z
+    assert waits == [0, 0, 0, 0, 1, 1]
+
+
 MASKS = [(True, False, False), (False, True, False), (False, False, True), (True, True, False), (True, False, True),
          (False, True, True)]
 
@@ -445,14 +467,15 @@ def test_bad_pointers_are_errors_before_any_launch_and_the_context_stays_usable(
     small = _sentinel((32 ** 3,))
     far = (1, 32, 1 << 34)   # planes 128 GiB apart: past the end of any allocation
     p = good.data_ptr()
-    for what, ptrs, st in (("not device memory", (host.ctypes.data, 0, 0), stride),
-                           ("not device memory", (p, 0, host.ctypes.data), stride),
-                           ("past the end", (0, small.data_ptr(), 0), far),
-                           ("overlap", (p, p + 8 * (32 ** 3 - 1), 0), stride),
-                           ("overlap", (0, p + 8, p), stride)):
-        with pytest.raises(omg.device.OmgError, match=what) as ex:
+    for what, ptrs, st in (("the pointer is not device memory", (host.ctypes.data, 0, 0), stride),
+                           ("the pointer is not device memory", (p, 0, host.ctypes.data), stride),
+                           ("the window reaches past the end of the pointer's allocation",
+                            (0, small.data_ptr(), 0), far),
+                           ("the windows of components 0 and 1 overlap", (p, p + 8 * (32 ** 3 - 1), 0), stride),
+                           ("the windows of components 1 and 2 overlap", (0, p + 8, p), stride)):
+        with pytest.raises(omg.device.OmgError) as ex:
             ctx.get_dense_grad(1, IPHI, ptrs, (0, 0, 0), n, st, -1.0)
-        assert "omg_get_dense_grad" in str(ex.value)
+        assert str(ex.value) == "omg_get_dense_grad: " + what
         assert _launches(be, "dense_grad") == 0
         assert (_bits(good) == U.SENTINEL).all() and (_bits(small) == U.SENTINEL).all()
         # the context stays usable
