@@ -33,24 +33,6 @@ static GcBC bc_for(omg_ctx* c, int lvl, int iv) {
   return g;
 }
 
-// The refinement-boundary ghosts of level lvl+1 are interpolated from level
-// lvl (its interior and tangential ghosts, box_gc_for_fine_neighbor,
-// m_ghost_cells.f90:500-577): every write of phi on lvl makes them stale.
-void rb_stale_above(omg_ctx* c, int lvl) {
-  if (Level* U = level_ptr(c, lvl + 1)) {
-    if (U->any_rb) U->phi_gc_ok = false;
-    U->rbgv_ok = false;   // (its refinement-boundary coarse parts read lvl)
-  }
-}
-// phi was written on a level: its ghost faces may no longer match a fill
-void phi_dirty(omg_ctx* c, int lvl) {
-  if (Level* L = level_ptr(c, lvl)) L->phi_gc_ok = L->gc_deferred = false;
-  rb_stale_above(c, lvl);
-}
-void phi_dirty_all(omg_ctx* c) {
-  for (auto& kv : c->levels) kv.second.phi_gc_ok = kv.second.rbgv_ok = kv.second.gc_deferred = false;
-}
-
 // Refinement-boundary faces whose ghosts a host callback sets instead of
 // sides_rb (mg%bc(nb,iv)%refinement_bnd, fill_refinement_bnd,
 // m_ghost_cells.f90:321-325): after a fill of the level has run on the device
@@ -120,11 +102,9 @@ void fill_gc_lvl(omg_ctx* c, int lvl, int iv) {
   if (lvl > c->highest) throw OmgError("fill_ghost_cells_lvl: lvl > highest_lvl");
   Level* L = level_ptr(c, lvl);
   if (!L) return;
-  if (iv == 1) {
-    res_before_write(c, L, L->d_phi);
-    L->phi_gc_ok = true;
-    L->gc_deferred = false;
-    rb_stale_above(c, lvl);   // (the ghosts it sets are read by lvl+1's interpolation)
+  if (iv == 1) {   // (the ghosts it sets are read by lvl+1's interpolation)
+    ready(c, lvl, kWrite);
+    wrote(c, lvl, kGcAll);
   }
   if (L->n) {
     Prof p(c, "fill_gc", (double)L->n * 6 * L->nc * L->nc, lvl);
@@ -144,23 +124,31 @@ void fill_gc_lvl(omg_ctx* c, int lvl, int iv) {
 // by the level's halo plan.  Both rounds are collective: the rhs refill is
 // decided by flags every rank changes alike (every rhs writer is a
 // collective call, include/omg.h), checked under OMG_CHECK_COLLECTIVE.
+// one round of the deep halo's bricks: variable iv (colour: phi's), w doubles each
+static void deep_round(omg_ctx* c, Level* L, const Transfer& T, int iv, int colour, int w) {
+  const LevelView V = L->view();
+  launch_deep_copy(V, iv, colour, w, T.d_send_items, T.n_send, L->d_sendbuf, false, c->stream);
+  exchange(c, T, L->d_sendbuf, L->d_recvbuf, nullptr, L->lvl);
+  launch_deep_copy(V, iv, colour, w, T.d_recv_items, T.n_recv, L->d_recvbuf, true, c->stream);
+}
+// the ghosts of this rank's faces toward other GPUs, by the level's halo plan
+static void face_round(omg_ctx* c, Level* L, int iv, hipStream_t st) {
+  launch_face_pack(L->view(), iv, L->halo.d_send_items, L->halo.n_send, L->d_sendbuf, st);
+  exchange(c, L->halo, L->d_sendbuf, L->d_recvbuf, st, L->lvl);
+  launch_unpack_faces(L->view(), iv, L->halo.d_recv_items, L->halo.n_recv, L->d_recvbuf, st);
+}
 static void deep_before(omg_ctx* c, Level* L, int colour) {
   if (!L->deep) return;
-  materialize_rhs(c, L);   // (its rhs round copies rhs as stored; a split level never has shifts pending)
-  const LevelView V = L->view();
+  ready(c, L->lvl, kRhs);   // (its rhs round copies rhs as stored; a split level never has shifts pending)
   if (c->check_collective && (allreduce(c, L->prox_rhs_ok ? 1.0 : 0.0, true) > 0.5) != L->prox_rhs_ok)
     throw OmgError("deep halo: the rhs refill decision differs across ranks (an rhs write was not collective)");
   if (!L->prox_rhs_ok) {
     Prof p(c, "deep_rhs", (double)L->deep_rhs.n_recv * 64, L->lvl);
-    launch_deep_copy(V, 2, 0, 64, L->deep_rhs.d_send_items, L->deep_rhs.n_send, L->d_sendbuf, false, c->stream);
-    exchange(c, L->deep_rhs, L->d_sendbuf, L->d_recvbuf, nullptr, L->lvl);
-    launch_deep_copy(V, 2, 0, 64, L->deep_rhs.d_recv_items, L->deep_rhs.n_recv, L->d_recvbuf, true, c->stream);
+    deep_round(c, L, L->deep_rhs, 2, 0, 64);
     L->prox_rhs_ok = true;
   }
   Prof p(c, "deep_phi", (double)L->deep_phi.n_recv * 32, L->lvl);
-  launch_deep_copy(V, 1, colour, 32, L->deep_phi.d_send_items, L->deep_phi.n_send, L->d_sendbuf, false, c->stream);
-  exchange(c, L->deep_phi, L->d_sendbuf, L->d_recvbuf, nullptr, L->lvl);
-  launch_deep_copy(V, 1, colour, 32, L->deep_phi.d_recv_items, L->deep_phi.n_recv, L->d_recvbuf, true, c->stream);
+  deep_round(c, L, L->deep_phi, 1, colour, 32);
 }
 // defer: on the comm stream, joined by the caller (faces_pending: only the
 // boxes with a face on another GPU wait for it, update_coarse's residual)
@@ -174,9 +162,7 @@ static void deep_after(omg_ctx* c, Level* L, bool defer = false) {
     L->faces_pending = true;
   }
   Prof p(c, "deep_faces", (double)L->halo.n_recv * L->nc * L->nc, L->lvl, st);
-  launch_face_pack(L->view(), 1, L->halo.d_send_items, L->halo.n_send, L->d_sendbuf, st);
-  exchange(c, L->halo, L->d_sendbuf, L->d_recvbuf, st, L->lvl);
-  launch_unpack_faces(L->view(), 1, L->halo.d_recv_items, L->halo.n_recv, L->d_recvbuf, st);
+  face_round(c, L, 1, st);
   if (L->faces_pending) HIPCHK(hipEventRecord(c->ev_comm, c->stream_comm));
 }
 // after a deep level's RES pass (res = phi - old, stored for the correction
@@ -186,14 +172,9 @@ static void deep_after(omg_ctx* c, Level* L, bool defer = false) {
 // same-GPU ones
 static void deep_res(omg_ctx* c, Level* L) {
   if (!L->deep) return;
-  const LevelView V = L->view();
   Prof p(c, "deep_res", (double)L->deep_rhs.n_recv * 64, L->lvl);
-  launch_deep_copy(V, 4, 0, 64, L->deep_rhs.d_send_items, L->deep_rhs.n_send, L->d_sendbuf, false, c->stream);
-  exchange(c, L->deep_rhs, L->d_sendbuf, L->d_recvbuf, nullptr, L->lvl);
-  launch_deep_copy(V, 4, 0, 64, L->deep_rhs.d_recv_items, L->deep_rhs.n_recv, L->d_recvbuf, true, c->stream);
-  launch_face_pack(V, 4, L->halo.d_send_items, L->halo.n_send, L->d_sendbuf, c->stream);
-  exchange(c, L->halo, L->d_sendbuf, L->d_recvbuf, nullptr, L->lvl);
-  launch_unpack_faces(V, 4, L->halo.d_recv_items, L->halo.n_recv, L->d_recvbuf, c->stream);
+  deep_round(c, L, L->deep_rhs, 4, 0, 64);
+  face_round(c, L, 4, c->stream);
 }
 
 // the deferred faces of deep_after have arrived (the main stream waits)
@@ -203,33 +184,48 @@ static void faces_join(omg_ctx* c, Level* L) {
   L->faces_pending = false;
 }
 
+// A pass over a split level with its halo under way: the boxes with faces on
+// other GPUs first (bnd), whose halo travels on the comm stream while the
+// others run (rest: it reads only its own boxes' ghost faces, and none of
+// those is remote; the unpack writes remote faces only, the halves `colours`).
+// rest is queued before the exchange is issued: the exchange may wait on the
+// host (the loopback transport waits for its peer's message), and rest needs
+// nothing from it.
+template <class Bnd, class Rest>
+static void split_overlap(omg_ctx* c, Level* L, int colours, Bnd bnd, Rest rest) {
+  bnd();
+  HIPCHK(hipEventRecord(c->ev_bnd, c->stream));
+  rest();
+  HIPCHK(hipStreamWaitEvent(c->stream_comm, c->ev_bnd, 0));
+  exchange(c, L->halo, L->d_sendbuf, L->d_recvbuf, c->stream_comm, L->lvl);
+  launch_unpack_faces(L->view(), 1, L->halo.d_recv_items, L->halo.n_recv, L->d_recvbuf, c->stream_comm, colours);
+  HIPCHK(hipEventRecord(c->ev_comm, c->stream_comm));
+  HIPCHK(hipStreamWaitEvent(c->stream, c->ev_comm, 0));
+}
+
 // smooth_boxes (m_multigrid.f90:404-424)
 // want_res: the level above takes k_gsrb3's correct_children form next, which
 // reads this level's res = phi - old: the last three substeps run as one
 // k_gsrb3 pass that also stores it (the plain substeps first); returns whether
 // that pass ran.
-// four: runs of four substeps as one k_gsrb4 pass (the down-smoothing when
-// the residual + restriction run unfused after it, OMG_BLOCK4)
-// defer_faces: a k_gsrb4 pass that ends the smoothing leaves its remote faces'
-// exchange in flight on the comm stream (deep_after), for update_coarse
-bool smooth_boxes(omg_ctx* c, int lvl, int n_cycle, int first_substep, int skip_last,
-                  bool want_res, bool four, bool defer_faces) {
+// block4: runs of four substeps as one k_gsrb4 pass (the down-smoothing when
+// the residual + restriction run unfused after it, OMG_BLOCK4); the one that
+// ends the smoothing leaves its remote faces' exchange in flight on the comm
+// stream (deep_after), for update_coarse
+bool smooth_boxes(omg_ctx* c, int lvl, int n_cycle, int first_substep, int skip_last, bool want_res, bool block4) {
   Level* L = level_ptr(c, lvl);
   const int n_sub = n_cycle * c->n_substeps - skip_last;
   bool res_done = false;
   if (!L) return false;
-  if (n_sub >= 1) rb_stale_above(c, lvl);
   // a pending phi shift is subtracted by the first tiled substep while it
   // loads (the values it reads are dead afterwards); otherwise applied now
   // (not next to refinement boundaries: their ghosts read the coarse level;
   // nor before a block pass with physical faces, whose ghosts take no shift)
   const bool absorb = L->shift_pending && c->smoother == OMG_SMOOTHER_GSRB && n_sub >= 1 &&
-                      (L->phi_gc_ok || L->gc_deferred) &&
-                      !L->has_rb && gs_tiled(L->nc, c->op, L->has_rb) && !(L->d_b3 && L->b3_phys);
-  if (L->shift_pending && !absorb) materialize_level(c, L);
+                      (L->phi_gc_ok || L->gc_deferred) && !L->has_rb && tiled_nc(L->nc) && !(L->d_b3 && L->b3_phys);
+  if (!absorb) ready(c, lvl, kPhi);
   if (c->smoother != OMG_SMOOTHER_GSRB) {
-    if (n_sub >= 1) res_before_write(c, L, L->d_phi);
-    materialize_rhs(c, L);   // (the lexicographic sweeps read rhs as stored)
+    ready(c, lvl, kGhosts | kRhs | (n_sub >= 1 ? kWrite : 0));
     // the register-ring kernel reads rhs from its ring-order copy, rebuilt
     // here when a write since the last build dropped it (update_coarse for
     // the levels below the top, every entry point that may change rhs)
@@ -273,7 +269,7 @@ bool smooth_boxes(omg_ctx* c, int lvl, int n_cycle, int first_substep, int skip_
         Prof p(c, "fill_gc", (double)L->n_physbox * 6 * L->nc * L->nc, lvl);
         launch_phys_gc(L->view(), bc, L->d_physbox, L->n_physbox, c->stream);
       }
-      L->phi_gc_ok = true;
+      wrote(c, lvl, kGcAll);
       return false;
     }
     for (int n = 1; n <= n_sub; n++) {
@@ -283,7 +279,7 @@ bool smooth_boxes(omg_ctx* c, int lvl, int n_cycle, int first_substep, int skip_
                       xlf ? L->d_xlay : nullptr);
       }
       if (xlf) {
-        L->phi_gc_ok = true;
+        wrote(c, lvl, kGcAll);
         if (L->n) {
           Prof p(c, "fill_gc", (double)L->n * 6 * L->nc * L->nc, lvl);
           launch_fill_tile_xl(L->sweep_view(), bc_for(c, lvl, 1), L->d_sendbuf, L->d_xlay, c->stream);
@@ -304,9 +300,8 @@ bool smooth_boxes(omg_ctx* c, int lvl, int n_cycle, int first_substep, int skip_
     // substep and a full fill follows it.
     const int e = n & 1;
     const bool odd = L->nc & 1;
-    if (n == 1 && absorb) phi_mean_ready(c);
-    const double* shift = (n == 1 && absorb) ? red_mean(c, 0) : nullptr;
-    if (n == 1) L->shift_pending = false;
+    const unsigned phi = n == 1 && absorb ? kPhiAbsorb : kPhi;
+    const double* shift = n == 1 && absorb ? red_mean(c, 0) : nullptr;
     // substeps n, n+1, n+2 in one pass (k_gsrb3) into phi's other buffer: it
     // reads the neighbours' cells in their boxes, which equal its ghosts only
     // when they are consistent (phi_gc_ok), and writes every ghost face
@@ -314,80 +309,52 @@ bool smooth_boxes(omg_ctx* c, int lvl, int n_cycle, int first_substep, int skip_
     B3Phys P3;
     const B3Phys* ph = nullptr;
     const bool b3 = b3_usable(c, lvl, P3, ph);
-    if (four && (n_sub - n + 1) % 4 == 0 && b3 && (!ph || c->block4_phys)) {
-      double* other = L->d_phi == L->d_data ? L->d_phi_buf : L->d_data;
-      res_before_write(c, L, other);
+    if (block4 && (n_sub - n + 1) % 4 == 0 && b3 && (!ph || c->block4_phys)) {
+      ready(c, lvl, phi | (ph ? kRhs : 0) | kWriteOther);   // (the form with physical faces takes no list)
       deep_before(c, L, 1 - e);
-      if (ph) materialize_rhs(c, L);   // (the form with physical faces takes no list)
       {
-        // (the level's pending rhs shifts are subtracted at the loads)
         Prof p(c, "smoother_gsrb4", 2.0 * L->n * L->nc * L->nc * L->nc, lvl);
-        launch_gsrb4(L->view(), other, L->d_b3, L->n_b3, c->op, c->lambda, e, shift, c->stream, nullptr, nullptr,
-                     ph, true, rhs_shifts(c, L));
+        launch_gsrb4(L->view(), other_phi(L), L->d_b3, L->n_b3, c->op, c->lambda, e, shift, c->stream, nullptr,
+                     nullptr, ph, true, rhs_shifts(c, L));
       }
-      L->d_phi = other;
-      if (L->gc_deferred) L->phi_gc_ok = true, L->gc_deferred = false;   // (it wrote every ghost face)
-      deep_after(c, L, defer_faces && n + 3 == n_sub);
+      wrote(c, lvl, kWriteOther | kGcAll);
+      deep_after(c, L, n + 3 == n_sub);
       n += 3;
       continue;
     }
     if (n + 2 <= n_sub && b3 && !(want_res && (n_sub - n + 1) % 3 != 0)) {
-      double* other = L->d_phi == L->d_data ? L->d_phi_buf : L->d_data;
       // the down-smoothing's last pass before k_smooth_resid (skip_last: it
       // runs the next substep, colour 0, and forms colour 0's ghosts itself
       // from colour 1, reading colour 1's only): push colour e = 1 alone
       // (a split level: both colours, its remote faces' ghosts arrive whole)
       const bool push1 = L->deep || !(skip_last == 1 && n + 2 == n_sub && e == 1);
       const bool res = want_res && n + 2 == n_sub && push1;
-      res_before_write(c, L, other);
-      materialize_rhs(c, L);   // (k_gsrb3 reads rhs as stored)
+      ready(c, lvl, phi | kRhs | kWriteOther);
       deep_before(c, L, 1 - e);
       {
         Prof p(c, res ? "smoother_gsrb3r" : "smoother_gsrb3", 1.5 * L->n * L->nc * L->nc * L->nc, lvl);
-        launch_gsrb3(L->view(), other, L->d_b3, L->n_b3, c->op, c->lambda, e, shift, c->stream, push1, nullptr,
+        launch_gsrb3(L->view(), other_phi(L), L->d_b3, L->n_b3, c->op, c->lambda, e, shift, c->stream, push1, nullptr,
                      nullptr, 1, res, ph);
       }
       res_done = res;
-      L->d_phi = other;
       // (its ghost faces: every one, colour e's only without push1, whose
       // colour-(1-e) halves k_smooth_resid forms itself)
-      if (L->gc_deferred) L->phi_gc_ok = true, L->gc_deferred = false;
+      wrote(c, lvl, kWriteOther | kGcAll);
       deep_after(c, L);
       if (res) deep_res(c, L);
       n += 2;
       continue;
     }
-    // (the one-substep kernels read the ghosts: a deferred fill runs first;
-    // and rhs as stored)
-    if (L->gc_deferred) fill_gc_lvl(c, lvl, 1);
-    res_before_write(c, L, L->d_phi);
-    materialize_rhs(c, L);
-    if (L->n_bnd && L->n_int && !odd && gs_tiled(L->nc, c->op, L->has_rb)) {
-      // boxes with faces on other GPUs first; their halo travels on the comm
-      // stream while the interior boxes run (the substep reads only its own
-      // box's ghost faces, and an interior box has no remote one; the unpack
-      // writes remote faces only)
+    ready(c, lvl, phi | kGhosts | kRhs | kWrite);
+    if (L->n_bnd && L->n_int && !odd && tiled_nc(L->nc)) {
       const int gvm = L->d_rbgv ? (L->rbgv_ok ? 2 : 1) : 0;
       if (gvm) L->rbgv_ok = true;
-      {
-        Prof p(c, "smoother_gsrb", 0.5 * L->n_bnd * L->nc * L->nc * L->nc, lvl);
+      auto substep = [&](const int* boxes, int n_boxes) {
+        Prof p(c, "smoother_gsrb", 0.5 * n_boxes * L->nc * L->nc * L->nc, lvl);
         launch_gs_substep(L->sweep_view(), c->op, c->lambda, e, 1 << e, view_of(c, lvl - 1), L->d_rb, L->has_rb,
-                          bc_for(c, lvl, 1), L->d_sendbuf, shift, c->stream, L->d_bnd, L->n_bnd, L->d_rbgv, gvm);
-      }
-      HIPCHK(hipEventRecord(c->ev_bnd, c->stream));
-      // the interior boxes are queued before the exchange is issued: the
-      // exchange may wait on the host (the loopback transport waits for its
-      // peer's message), and the interior substep needs nothing from it
-      {
-        Prof p(c, "smoother_gsrb", 0.5 * L->n_int * L->nc * L->nc * L->nc, lvl);
-        launch_gs_substep(L->sweep_view(), c->op, c->lambda, e, 1 << e, view_of(c, lvl - 1), L->d_rb, L->has_rb,
-                          bc_for(c, lvl, 1), L->d_sendbuf, shift, c->stream, L->d_int, L->n_int, L->d_rbgv, gvm);
-      }
-      HIPCHK(hipStreamWaitEvent(c->stream_comm, c->ev_bnd, 0));
-      exchange(c, L->halo, L->d_sendbuf, L->d_recvbuf, c->stream_comm, lvl);
-      launch_unpack_faces(L->view(), 1, L->halo.d_recv_items, L->halo.n_recv, L->d_recvbuf, c->stream_comm);
-      HIPCHK(hipEventRecord(c->ev_comm, c->stream_comm));
-      HIPCHK(hipStreamWaitEvent(c->stream, c->ev_comm, 0));
+                          bc_for(c, lvl, 1), L->d_sendbuf, shift, c->stream, boxes, n_boxes, L->d_rbgv, gvm);
+      };
+      split_overlap(c, L, 3, [&] { substep(L->d_bnd, L->n_bnd); }, [&] { substep(L->d_int, L->n_int); });
       finish_rb(c, L, 1);
       if (!L->phi_gc_ok) fill_gc_lvl(c, lvl, 1);
       else rb_host_fixup(c, L, 1);
@@ -409,58 +376,12 @@ bool smooth_boxes(omg_ctx* c, int lvl, int n_cycle, int first_substep, int skip_
   return res_done;
 }
 
-static bool tiled_level(omg_ctx* c, const Level* L) {
-  (void)c;
-  return L && tiled_nc(L->nc);
-}
-
-// A pending res (Level::res_pend).  On the top level of a stand-alone cycle
-// over the whole tree nothing reads the res that update_coarse's residual
-// stores: its restriction leaves the same launch from registers and LDS, the
-// up leg reads the coarse level's res, and the next cycle's update_coarse (or
-// this cycle's max residual) overwrites every box.  That launch therefore runs
-// without the store (k_resid_restrict's STORE = false) and the level notes the
-// phi buffer it read.  The level's passes alternate between its two buffers,
-// so that buffer is still whole when the cycle ends, ghost faces included,
-// and rhs reads the same through its shifts, whether stored or listed:
-// the storing form over the same inputs gives the bits the skipped store
-// would have.  Whoever may read res stores it first (enter(), the cycles that
-// do not overwrite it, an operator change), and so does any pass about to
-// write the noted buffer (res_before_write).
-void materialize_res(omg_ctx* c, Level* L) {
-  if (!L->res_pend) return;
-  L->res_pend = false;
-  if (!L->n) return;
-  LevelView V = L->sweep_view();
-  V.phi = L->res_src;
-  Prof p(c, "residual", (double)L->n * L->nc * L->nc * L->nc, L->lvl);
-  launch_resid_restrict(V, empty_view(), c->op, c->lambda, nullptr, 0, nullptr, nullptr, c->stream, nullptr, 0,
-                        rhs_shifts(c, L));
-}
-void materialize_res_all(omg_ctx* c) {
-  for (auto& kv : c->levels) materialize_res(c, &kv.second);
-}
-// before a write of the level's phi buffer buf (interior or ghost faces)
-void res_before_write(omg_ctx* c, Level* L, const double* buf) {
-  if (!L || !L->res_pend || L->res_src != buf) return;
-  // inside a stand-alone cycle: these counts make the level's own passes write
-  // the buffer, every cycle would pay the second launch
-  if (c->in_full_cycle) L->res_pend_off = true;
-  materialize_res(c, L);
-}
-// whether update_coarse's residual on a stand-alone cycle's top level may
-// leave its res unstored
-static bool res_pend_ok(omg_ctx* c, const Level* L) {
-  return c->n_ranks == 1 && !c->capturing && !c->no_res_pend && L->n && tiled_level(c, L) && !L->res_pend_off;
-}
-
 void residual_lvl(omg_ctx* c, int lvl, unsigned long long* maxbits) {
   Level* L = level_ptr(c, lvl);
   if (!L || L->n == 0) return;
-  L->res_pend = false;   // (every box's res is written below)
-  if (!tiled_level(c, L)) materialize_rhs(c, L);
+  ready(c, lvl, kPhi | kGhosts | (tiled_nc(L->nc) ? 0 : kRhs) | kResWrite);
   Prof p(c, "residual", (double)L->n * L->nc * L->nc * L->nc, lvl);
-  if (tiled_level(c, L))
+  if (tiled_nc(L->nc))
     launch_resid_restrict(L->sweep_view(), empty_view(), c->op, c->lambda, maxbits, 0, nullptr, nullptr, c->stream,
                           nullptr, 0, rhs_shifts(c, L));
   else
@@ -505,8 +426,7 @@ static void restrict_remote(omg_ctx* c, int iv, int lvl) {
 // mg_restrict_lvl (m_restrict.f90:83-114)
 void restrict_lvl(omg_ctx* c, int iv, int lvl) {
   if (lvl <= c->lowest) throw OmgError("cannot restrict lvl <= lowest_lvl");
-  if (iv == 1) phi_dirty(c, lvl - 1);
-  if (Level* Cl = level_ptr(c, lvl - 1); Cl && iv == 1) res_before_write(c, Cl, Cl->d_phi);
+  if (iv == 1) ready(c, lvl - 1, kWrite), wrote(c, lvl - 1, kGcStale);
   Level* F = level_ptr(c, lvl);
   restrict_remote(c, iv, lvl);
   if (F && F->n_pairs) {
@@ -520,10 +440,9 @@ void restrict_lvl(omg_ctx* c, int iv, int lvl) {
 void prolong(omg_ctx* c, int lvl, int iv, int iv_to, int add) {
   if (lvl == c->highest) throw OmgError("cannot prolong highest level");
   if (lvl < c->lowest) throw OmgError("cannot prolong below lowest level");
-  if (iv_to == 1) phi_dirty(c, lvl + 1);
+  if (iv_to == 1) ready(c, lvl + 1, kWrite), wrote(c, lvl + 1, kGcStale);
   Level* F = level_ptr(c, lvl + 1);
   Level* C = level_ptr(c, lvl);
-  if (iv_to == 1) res_before_write(c, F, F->d_phi);
   const LevelView FV = view_of(c, lvl + 1), CV = view_of(c, lvl);
   if (c->n_ranks > 1 && F && C && (F->prol.n_send || F->prol.n_recv)) {
     launch_prolong_pack(CV, FV, iv, F->prol.d_send_items, F->prol.n_send, C->d_sendbuf, c->stream);
@@ -575,28 +494,25 @@ static bool smooth_resid_ok(omg_ctx* c, int lvl) {
 // (its top level, TailArgs::top_crhs): only the residual and the restriction here
 void update_coarse(omg_ctx* c, int lvl, bool fused, bool tail_crhs, bool res_may_pend) {
   Level* F = level_ptr(c, lvl);
-  if (F) F->res_pend = false;   // (every branch below writes res of every box of lvl, or leaves it pending anew)
+  // (every branch below writes res of every box of lvl, or leaves it pending
+  // anew; k_resid_restrict takes the level's pending rhs shifts)
+  if (F) ready(c, lvl, kPhi | kGhosts | (fused || !tiled_nc(F->nc) ? kRhs : 0) | kResWrite);
+  // the coarse level's rhs and res are rewritten below; restriction overwrites
+  // every box of an all-parents level (interior), and the fill below every
+  // ghost face.  (Its phi is written once F's stored coarse parts were read.)
   if (Level* Cl = level_ptr(c, lvl - 1)) {
-    Cl->rhs_lex_ok = Cl->prox_rhs_ok = false;   // its rhs is rewritten below
-    materialize_res(c, Cl);   // (its phi, rhs and res are rewritten below; never pending in a cycle)
-    // restriction overwrites every box of an all-parents level (interior), and
-    // the fill below every ghost face: a pending shift there is dead
-    if (Cl->all_parents) Cl->shift_pending = false;
-    else materialize_level(c, Cl);
-    materialize_rhs(c, Cl);
+    ready(c, lvl - 1, (Cl->all_parents ? kPhiDead : kPhi) | kRhsWrite);
+    wrote(c, lvl - 1, kRhsWrite);
   }
-  // (k_resid_restrict takes the level's pending rhs shifts; the fused forms
-  // and the untiled residual read rhs as stored)
-  if (F && (fused || !tiled_level(c, F))) materialize_rhs(c, F);
-  if (F && F->n && tiled_level(c, F)) {
+  if (F && F->n && tiled_nc(F->nc)) {
     // The stored refinement-boundary coarse parts of lvl (d_rbgv) were formed
     // from lvl-1 as it stands until the restriction below writes it, which is
-    // what the fused down-substep's ghosts need; read the flag before
-    // phi_dirty drops it.  (The coarse boxes across those faces are leaves:
-    // the restriction never writes them.)
+    // what the fused down-substep's ghosts need; read the flag before the
+    // write of lvl-1 drops it.  (The coarse boxes across those faces are
+    // leaves: the restriction never writes them.)
     const bool rbgv = F->rbgv_ok;
     // residual + restriction of phi and res in one pass (omg_tiles.hip)
-    phi_dirty(c, lvl - 1);
+    ready(c, lvl - 1, kWrite), wrote(c, lvl - 1, kGcStale);
     if (fused && F->has_remote) {
       // multi-GPU: boxes with a face on another GPU take the unfused pair (the
       // substep, its halo on the comm stream, then the residual); the others
@@ -611,25 +527,18 @@ void update_coarse(omg_ctx* c, int lvl, bool fused, bool tail_crhs, bool res_may
       // forms them whole once the fused launch is done, before the boundary
       // boxes' residual reads them.
       const bool faces = F->any_phys || F->any_rb;
-      {
+      split_overlap(c, F, 1, [&] {
         Prof p(c, "smoother_gsrb", 0.5 * F->n_bnd * F->nc * F->nc * F->nc, lvl);
         launch_gs_substep(F->view(), c->op, c->lambda, 0, faces ? 1 | 4 : 1, view_of(c, lvl - 1), F->d_rb,
                           F->has_rb, bc_for(c, lvl, 1), F->d_sendbuf, nullptr, c->stream, F->d_bnd, F->n_bnd,
                           rbgv ? F->d_rbgv : nullptr, rbgv ? 2 : 0);
-      }
-      HIPCHK(hipEventRecord(c->ev_bnd, c->stream));
-      {   // (queued before the exchange is issued, as in smooth_boxes)
+      }, [&] {
         Prof p(c, "smooth_resid", (double)F->n_int * F->nc * F->nc * F->nc, lvl);
         if (!launch_smooth_resid(F->sweep_view(), view_of(c, lvl - 1), c->op, c->lambda, 1, F->d_parent_local,
                                  F->d_dix, c->stream, F->d_int, F->n_int, bc_for(c, lvl, 1), F->has_rb, F->has_phys,
                                  rbgv ? F->d_rbgv : nullptr))
           throw OmgError("smooth_resid: not available for this level");
-      }
-      HIPCHK(hipStreamWaitEvent(c->stream_comm, c->ev_bnd, 0));
-      exchange(c, F->halo, F->d_sendbuf, F->d_recvbuf, c->stream_comm, lvl);
-      launch_unpack_faces(F->view(), 1, F->halo.d_recv_items, F->halo.n_recv, F->d_recvbuf, c->stream_comm, 1);
-      HIPCHK(hipEventRecord(c->ev_comm, c->stream_comm));
-      HIPCHK(hipStreamWaitEvent(c->stream, c->ev_comm, 0));
+      });
       if (faces && F->n_bndface) {
         Prof p(c, "face_gc", (double)F->n_bndface * 6 * F->nc * F->nc, lvl);
         launch_face_gc(F->view(), view_of(c, lvl - 1), bc_for(c, lvl, 1), F->d_bndface, F->n_bndface, c->stream);
@@ -686,8 +595,7 @@ void update_coarse(omg_ctx* c, int lvl, bool fused, bool tail_crhs, bool res_may
   // neighbours' boundary cells itself instead of waiting for their pushes)
   if (C && C->n && !C->parents.empty() && !C->has_rb && !C->has_remote && !c->no_fill_tile && !c->no_fill_crhs &&
       (C->nc == 16 || C->nc == 8 || C->nc == 4)) {
-    C->phi_gc_ok = true;
-    rb_stale_above(c, lvl - 1);
+    ready(c, lvl - 1, kWrite), wrote(c, lvl - 1, kGcAll);
     {
       Prof p(c, "fill_crhs", (double)C->n * C->nc * C->nc * C->nc, lvl - 1);
       launch_fill_crhs(C->sweep_view(), c->op, c->lambda, bc_for(c, lvl - 1, 1), C->d_parmask, c->stream);
@@ -726,14 +634,11 @@ static bool prolong_smooth(omg_ctx* c, int lvl) {
                      !(F->rbh.count(1) && F->rbh.at(1).n);
   if (c->no_fuse_up || !F || !C || !F->prolong_smooth_ok || c->smoother != OMG_SMOOTHER_GSRB ||
       (c->op != OP_LPL && c->op != OP_HELM) ||
-      c->n_cycle_up < 1 || (F->has_rb && !rb_ok) || (F->has_remote && !F->n_int) || !gs_tiled(F->nc, c->op, F->has_rb) ||
+      c->n_cycle_up < 1 || (F->has_rb && !rb_ok) || (F->has_remote && !F->n_int) || !tiled_nc(F->nc) ||
       !((size_t)F->n == 8 * C->parents.size() || C->nc * 2 == F->nc) ||
       (c->n_ranks > 1 && (F->prol.n_send || F->prol.n_recv)))
     return false;
-  if (F->shift_pending) materialize_level(c, F);
-  res_before_write(c, F, F->d_phi);
-  materialize_rhs(c, F);   // (k_prolong_smooth and the one-substep kernel read rhs as stored)
-  rb_stale_above(c, lvl + 1);
+  ready(c, lvl + 1, kPhi | kGhosts | kRhs | kWrite);
   const bool split = F->has_remote;
   {
     const int n = split ? F->n_int : F->n;
@@ -767,7 +672,7 @@ static bool prolong_smooth(omg_ctx* c, int lvl) {
   }
   // colour-0 ghost halves hold pre-correction values, but the next substep
   // reads only colour 1 and pushes colour 0 itself
-  F->phi_gc_ok = true;
+  wrote(c, lvl + 1, kGcAll);
   return true;
 }
 
@@ -793,10 +698,9 @@ static int correct_block3(omg_ctx* c, int l, bool res_ready, bool defer_gc = fal
   if (!block3c_ok(c, F) || !C || !C->phi_gc_ok || C->shift_pending) return 0;
   // (a split level: only from the coarse res, whose proxies deep_res filled)
   if (F->deep && !res_ready) return 0;
-  if (F->shift_pending) materialize_level(c, F);
-  rb_stale_above(c, l);
-  double* other = F->d_phi == F->d_data ? F->d_phi_buf : F->d_data;
-  res_before_write(c, F, other);
+  const bool four = res_ready && c->block4 && !c->no_block4p && c->n_cycle_up * c->n_substeps >= 4;
+  ready(c, l, kPhi | (four ? 0 : kRhs) | kWriteOther);   // (k_gsrb4 takes the rhs shifts)
+  double* other = other_phi(F);
   const LevelView cv = C->view();
   int done = 3;
   deep_before(c, F, 0);   // (the pass reads colour 0, before the correction)
@@ -806,7 +710,7 @@ static int correct_block3(omg_ctx* c, int l, bool res_ready, bool defer_gc = fal
   // writes per box are ghost faces), and the ghosts are filled if anything
   // else comes first (Level::gc_deferred)
   bool deferred = false;
-  if (res_ready && c->block4 && !c->no_block4p && c->n_cycle_up * c->n_substeps >= 4) {
+  if (four) {
     // (one rank: every rank decides its fills alike, see fas_vcycle)
     deferred = defer_gc && c->n_ranks == 1 && c->n_cycle_up * c->n_substeps == 4 && !F->deep && !F->b3_phys &&
                !c->no_defer_gc;
@@ -815,15 +719,12 @@ static int correct_block3(omg_ctx* c, int l, bool res_ready, bool defer_gc = fal
                  nullptr, !deferred, rhs_shifts(c, F));
     done = 4;
   } else {
-    materialize_rhs(c, F);   // (k_gsrb3 reads rhs as stored)
     Prof p(c, "smoother_gsrb3p", 1.5 * F->n * F->nc * F->nc * F->nc, l);
     launch_gsrb3(F->view(), other, F->d_b3, F->n_b3, c->op, c->lambda, 1, nullptr, c->stream, true, &cv, F->d_b3c,
                  res_ready ? 2 : 1);
   }
-  F->d_phi = other;
+  wrote(c, l, kWriteOther | (deferred ? kGcNone : kGcAll));
   deep_after(c, F);
-  F->phi_gc_ok = !deferred;
-  F->gc_deferred = deferred;
   return done;
 }
 
@@ -847,8 +748,7 @@ static void correct_and_fill(omg_ctx* c, int lvl, bool then_gsrb = false, bool s
   Level* C = level_ptr(c, lvl);
   if (save_old && (then_gsrb || !correct_fill_fused(c, lvl)))
     throw OmgError("internal: old = phi fused into an unfused correction");
-  if (F) res_before_write(c, F, F->d_phi);
-  rb_stale_above(c, lvl + 1);
+  ready(c, lvl + 1, kPhi | kGhosts | kWrite);
   if (correct_fill_fused(c, lvl)) {
     // every parent here has all its children on this GPU (no prolongation
     // traffic, every fine box has a local parent): the children form res
@@ -864,7 +764,7 @@ static void correct_and_fill(omg_ctx* c, int lvl, bool then_gsrb = false, bool s
                           F->h_rb.empty() ? nullptr : F->d_rb);
     }
     finish_halo(c, F, 1);
-    F->phi_gc_ok = true;
+    wrote(c, lvl + 1, kGcAll);
     return;
   }
   correct_children(c, lvl);
@@ -933,12 +833,11 @@ static void run_tail(omg_ctx* c, int top, bool top_crhs) {
   A.n_lvls = top - c->lowest + 1;
   for (int l = c->lowest; l <= top; l++) {
     Level* L = level_ptr(c, l);
-    if (L->shift_pending) {
-      if (L->all_parents && l < top) L->shift_pending = false;   // overwritten by the restriction
-      else materialize_level(c, L);
-    }
-    materialize_rhs(c, L);   // (the tail reads and writes rhs as stored)
-    L->rhs_lex_ok = L->prox_rhs_ok = false;   // the tail writes the rhs of the levels below its top
+    // (phi of an all-parents level below the top is overwritten by the
+    // restriction; the tail reads rhs as stored and writes that of the levels
+    // below its top)
+    ready(c, l, (L->all_parents && l < top ? kPhiDead : kPhi) | kRhs | kWrite);
+    wrote(c, l, kRhsWrite);
     TailLevel& T = A.lv[l - c->lowest];
     T.L = L->view();
     T.bc = bc_for(c, l, 1);
@@ -990,8 +889,7 @@ static void run_tail(omg_ctx* c, int top, bool top_crhs) {
     for (int i = 1; i < 64 && h[i]; i++) std::fprintf(stderr, " %.1f", (h[i] - h[i - 1]) * 0.01);
     std::fprintf(stderr, "\n");
   }
-  for (int l = c->lowest; l <= top; l++) level_ptr(c, l)->phi_gc_ok = true;
-  rb_stale_above(c, top);
+  for (int l = c->lowest; l <= top; l++) wrote(c, l, kGcAll);
 }
 
 // Failure detection: the device max residual is an exact max of
@@ -1010,30 +908,26 @@ double fas_vcycle(omg_ctx* c, int highest_lvl, bool want_max_res, bool standalon
   const bool has_highest = highest_lvl >= c->lowest;
   const int min_lvl = c->lowest, max_lvl = has_highest ? highest_lvl : c->highest;
   const bool full = standalone && !has_highest;   // a stand-alone cycle over the whole tree
-  // A res left pending by the previous stand-alone cycle (materialize_res) is
+  // (nothing below changes which levels the coarse tail can hold)
+  const int top = tail_top(c, max_lvl);
+  const bool tail = top >= min_lvl && !c->no_tail;
+  const bool tail_crhs = tail && max_lvl > top && tail_crhs_ok(c, top);
+  // A res left pending by the previous stand-alone cycle (Level::res_pend) is
   // dead when this cycle's update_coarse runs on that level, which writes
   // every box of it (or leaves it pending anew); decided here, before this
   // cycle's rhs mean joins the list and its first pass writes the buffer.
   // Any other cycle (partial, inside FMG, or one whose coarse tail holds the
   // level) leaves that res as the reference does: it is stored first.
-  {
-    const int tt = tail_top(c, max_lvl);
-    const bool top_updates = full && max_lvl > min_lvl && !(tt >= min_lvl && !c->no_tail && max_lvl <= tt);
-    for (auto& kv : c->levels) {
-      if (top_updates && kv.first == max_lvl) kv.second.res_pend = false;
-      else materialize_res(c, &kv.second);
-    }
-  }
+  const bool top_updates = full && max_lvl > min_lvl && !(tail && max_lvl <= top);
+  materialize_res_all(c, top_updates ? max_lvl : INT_MIN);
   // a pending phi shift (previous stand-alone cycle) is absorbed by the first
   // substep on max_lvl or dropped where restriction overwrites a level
   if (c->phi_shift_pending) {
     if (!full) {
       materialize_phi(c);
     } else {
-      for (auto& kv : c->levels) {
-        Level& L = kv.second;
-        if (L.shift_pending && L.lvl != max_lvl && !L.all_parents) materialize_level(c, &L);
-      }
+      for (auto& kv : c->levels)
+        if (kv.first != max_lvl && !kv.second.all_parents) ready(c, kv.first, kPhi);
     }
   }
   // rhs shifts a stand-alone cycle left pending stay so through the next one
@@ -1066,20 +960,17 @@ double fas_vcycle(omg_ctx* c, int highest_lvl, bool want_max_res, bool standalon
     // changed since the deferral was made, and with n_cycle_down = 0 (a
     // zero-trip loop in the reference, m_multigrid.f90:407) smooth_boxes
     // launches nothing and update_coarse's residual reads the ghosts next
-    if (L && L->gc_deferred && c->smoother == OMG_SMOOTHER_GSRB && tail_top(c, max_lvl) < max_lvl &&
+    if (L && L->gc_deferred && c->smoother == OMG_SMOOTHER_GSRB && top < max_lvl &&
         c->n_cycle_down * c->n_substeps >= 1)
       need = false;
     if (c->n_ranks > 1 && c->check_collective && (allreduce(c, need ? 1.0 : 0.0, true) > 0.5) != need)
       throw OmgError("mg_fas_vcycle: the stand-alone fill decision differs across ranks "
                      "(an upload of phi was not made on every rank)");
     if (need) {
-      if (L) materialize_level(c, L);
+      ready(c, max_lvl, kPhi);
       fill_gc_lvl(c, max_lvl, 1);
     }
   }
-  const int top = tail_top(c, max_lvl);
-  const bool tail = top >= min_lvl && !c->no_tail;
-  const bool tail_crhs = tail && max_lvl > top && tail_crhs_ok(c, top);
   for (int l = max_lvl; l >= min_lvl + 1; l--) {
     if (tail && l <= top) break;
     // four substeps per pass, then the unfused residual (k_resid_restrict):
@@ -1096,10 +987,7 @@ double fas_vcycle(omg_ctx* c, int highest_lvl, bool want_max_res, bool standalon
     // to a residual that gathers the neighbours' boundary cells instead took
     // C3's down pass 837 -> 713 us and the residual 590 -> 750 us, the x faces'
     // cells 64 B apart in the neighbours' boxes; profiles/r06/s19_defer_down_ab.txt)
-    smooth_boxes(c, l, c->n_cycle_down, 1, fused ? 1 : 0, false, four, four);
-    // (update_coarse reads the level's ghosts: no smoothing above consumed a
-    // deferral, e.g. a cycle that is not stand-alone with n_cycle_down = 0)
-    if (Level* Fd = level_ptr(c, l); Fd && Fd->gc_deferred) fill_gc_lvl(c, l, 1);
+    smooth_boxes(c, l, c->n_cycle_down, 1, fused ? 1 : 0, false, four);
     update_coarse(c, l, fused, tail_crhs && l == top + 1, full && l == max_lvl);
     faces_join(c, level_ptr(c, l));   // (update_coarse joined them; defensive)
   }
@@ -1137,16 +1025,11 @@ double fas_vcycle(omg_ctx* c, int highest_lvl, bool want_max_res, bool standalon
     int pro = 0;
     if (!want_res && (pro = correct_block3(c, l, res_ready, full && l == max_lvl && !want_max_res)) > 0) {
       done = smooth_boxes(c, l, c->n_cycle_up, pro + 1);
+    } else if (prolong_smooth(c, l - 1)) {
+      done = smooth_boxes(c, l, c->n_cycle_up, 2, 0, want_res);
     } else {
-      // (the other correction paths read the level's ghosts: deferred ones are
-      // filled first)
-      if (Level* Fd = level_ptr(c, l); Fd && Fd->gc_deferred) fill_gc_lvl(c, l, 1);
-      if (prolong_smooth(c, l - 1)) {
-        done = smooth_boxes(c, l, c->n_cycle_up, 2, 0, want_res);
-      } else {
-        correct_and_fill(c, l - 1, c->smoother == OMG_SMOOTHER_GSRB && c->n_cycle_up >= 1);
-        done = smooth_boxes(c, l, c->n_cycle_up, 1, 0, want_res);
-      }
+      correct_and_fill(c, l - 1, c->smoother == OMG_SMOOTHER_GSRB && c->n_cycle_up >= 1);
+      done = smooth_boxes(c, l, c->n_cycle_up, 1, 0, want_res);
     }
     res_ready = done;
   }

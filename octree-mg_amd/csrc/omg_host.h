@@ -248,13 +248,46 @@ void free_levels(omg_ctx* c);
 bool b3_usable(omg_ctx* c, int lvl, B3Phys& P, const B3Phys*& ph);
 void build_plan(omg_ctx* c);
 
-// --- omg_cycle.cpp
+// --- omg_lazy.cpp: the lazy per-level state (omg_internal.h, above Level's
+// lazy fields).  What a pass on a level reads and writes: ready() before its
+// launch makes the level fit for it, wrote() after it records what it left.
+enum Pass : unsigned {
+  kPhi = 1,           // reads phi as stored: a pending mean is applied first
+  kPhiAbsorb = 2,     // subtracts the pending mean while loading (its shift argument, red_mean)
+  kPhiDead = 4,       // overwrites every value of phi unread: a pending mean is dropped
+  kGhosts = 8,        // reads phi's ghost faces (the block passes read none of the same-GPU ones)
+  kRhs = 16,          // reads rhs as stored (a pass that takes rhs_shifts says nothing)
+  kRhsWrite = 32,     // writes rhs
+  kResWrite = 64,     // writes res of every box
+  kWrite = 128,       // writes d_phi
+  kWriteOther = 256,  // writes other_phi, which becomes d_phi
+  kGcAll = 512, kGcNone = 1024, kGcStale = 2048,   // wrote(): the ghost faces it left (none of these: as they were)
+};
+void ready(omg_ctx* c, int lvl, unsigned pass);
+void wrote(omg_ctx* c, int lvl, unsigned pass);
+double* other_phi(const Level* L);
 void rb_stale_above(omg_ctx* c, int lvl);
 void phi_dirty(omg_ctx* c, int lvl);
 void phi_dirty_all(omg_ctx* c);
+// (dead_lvl: that level's cycle overwrites its res, a pending one is dropped)
+void materialize_res_all(omg_ctx* c, int dead_lvl = INT_MIN);
+bool res_pend_ok(omg_ctx* c, const Level* L);
+void phi_mean_ready(omg_ctx* c);
+void materialize_phi(omg_ctx* c);
+RhsShifts rhs_shifts(omg_ctx* c, const Level* L);
+void materialize_rhs_all(omg_ctx* c);
+// the smoothing counts, the smoother or the operator changed (rhs_pend_off and res_pend_off)
+void rhs_pend_retry(omg_ctx* c);
+bool rhs_pend_ok(omg_ctx* c, const Level* L);
+void drop_rhs_lex(omg_ctx* c);
+void drop_rhs_cache(omg_ctx* c);
+void enter(omg_ctx* c, bool writes = true);
+
+// --- omg_cycle.cpp
 void fill_gc_lvl(omg_ctx* c, int lvl, int iv);
+// block4: runs of four substeps as one k_gsrb4 pass, the last one's remote faces left in flight
 bool smooth_boxes(omg_ctx* c, int lvl, int n_cycle, int first_substep = 1, int skip_last = 0,
-                  bool want_res = false, bool four = false, bool defer_faces = false);
+                  bool want_res = false, bool block4 = false);
 void residual_lvl(omg_ctx* c, int lvl, unsigned long long* maxbits);
 double max_residual_lvl(omg_ctx* c, int lvl);
 void restrict_lvl(omg_ctx* c, int iv, int lvl);
@@ -262,11 +295,6 @@ void prolong(omg_ctx* c, int lvl, int iv, int iv_to, int add);
 // res_may_pend: the caller is a stand-alone cycle on its top level, whose
 // stored res nothing reads before it is overwritten (Level::res_pend)
 void update_coarse(omg_ctx* c, int lvl, bool fused = false, bool tail_crhs = false, bool res_may_pend = false);
-// a level's res left unstored by update_coarse: written out / before a write
-// of the phi buffer `buf` of the level that it would be recomputed from
-void materialize_res(omg_ctx* c, Level* L);
-void materialize_res_all(omg_ctx* c);
-void res_before_write(omg_ctx* c, Level* L, const double* buf);
 void correct_children(omg_ctx* c, int lvl);
 void check_finite_res(double r, const char* where);
 double fas_vcycle(omg_ctx* c, int highest_lvl, bool want_max_res, bool standalone);
@@ -283,17 +311,8 @@ void phi_bc_store(omg_ctx* c);
 // --- omg_mean.cpp
 enum { kChPhi = 0, kChRhs = 1 };
 double* red_mean(omg_ctx* c, int ch);
+void mean_device(omg_ctx* c, int ch, double* mean);
 double get_sum(omg_ctx* c, int iv);
-void phi_mean_ready(omg_ctx* c);
-void materialize_level(omg_ctx* c, Level* L);
-void materialize_phi(omg_ctx* c);
-RhsShifts rhs_shifts(omg_ctx* c, const Level* L);
-void materialize_rhs(omg_ctx* c, Level* L);
-void materialize_rhs_all(omg_ctx* c);
-// the smoothing counts, the smoother or the operator changed (rhs_pend_off and res_pend_off)
-void rhs_pend_retry(omg_ctx* c);
-void drop_rhs_lex(omg_ctx* c);
-void enter(omg_ctx* c, bool writes = true);
 enum { kPlain = 0, kInCycle = 1 };
 void subtract_mean(omg_ctx* c, int iv, int ghosts, int mode = kPlain);
 

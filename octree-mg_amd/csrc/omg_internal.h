@@ -222,12 +222,72 @@ struct Level {
   Transfer repl;
   double* d_data = nullptr;
   double* d_phi = nullptr;              // phi (d_data's var 1)
-  bool phi_gc_ok = false;               // phi's ghost faces equal what a fill would give
-  // phi's ghost faces are stale only because the level's last pass left them
-  // unwritten (the V-cycle's last up pass, correct_block3's defer_gc): the
-  // reference's ghosts are a fill of the interior, which every ghost reader
-  // runs first (fill_gc_lvl); the block passes read no ghosts on such a level
+  // ---------------------------------------------------------------------
+  // The lazy state: five things a level leaves unwritten until somebody
+  // needs them.  omg_lazy.cpp keeps them: every pass says what it reads and
+  // writes (Pass, omg_host.h), ready() before it stores, applies, fills or
+  // writes out what that needs, in this order, and wrote() after it records
+  // what it left; enter() does all of it for the entry points.
+  //
+  // 1. The unstored res.  On the top level of a stand-alone cycle over the
+  // whole tree nothing reads the res that update_coarse's residual stores:
+  // its restriction leaves the same launch from registers and LDS, the up leg
+  // reads the coarse level's res, and the next cycle's update_coarse (or this
+  // cycle's max residual) overwrites every box.  That launch therefore runs
+  // without the store (k_resid_restrict's STORE = false) and the level notes
+  // the phi buffer it read, res_src (d_data or d_phi_buf).  The level's
+  // passes alternate between its two buffers, so that buffer is still whole
+  // when the cycle ends, ghost faces included, and rhs reads the same through
+  // its shifts, whether stored or listed: the storing form over the same
+  // inputs gives the bits the skipped store would have.  Whoever may read
+  // res stores it first (enter(), the cycles that do not overwrite it, an
+  // operator change), and so does any pass about to write the noted buffer
+  // or rhs.  res_pend_off: a pass of a stand-alone cycle had to do that, so
+  // the level's cycles store at once until the smoothing counts, the smoother
+  // or the operator change (rhs_pend_retry).
+  bool res_pend = false;
+  double* res_src = nullptr;
+  bool res_pend_off = false;
+  // 2. The pending phi mean: phi -= mean still to apply (left by a
+  // stand-alone cycle's subtract_mean; omg_ctx::phi_shift_pending: on some
+  // level; phi_mean_on_side: the mean itself still on the side stream).  The
+  // first tiled substep or block pass subtracts it while loading, a level
+  // that restriction overwrites drops it, anything else that reads phi has
+  // it applied first.
+  bool shift_pending = false;
+  // 3. Deferred ghost faces.  phi_gc_ok: phi's ghost faces equal what a fill
+  // would give.  gc_deferred: they are stale only because the level's last
+  // pass left them unwritten (the V-cycle's last up pass, correct_block3's
+  // defer_gc): the reference's ghosts are a fill of the interior, which runs
+  // before every ghost reader; the block passes read no ghosts on such a level.
+  bool phi_gc_ok = false;
   bool gc_deferred = false;
+  // 4. The pending rhs shifts.  mg_fas_vcycle begins every periodic cycle
+  // with rhs <- rhs - mean(rhs) (m_multigrid.f90:245-276).  A stand-alone
+  // cycle leaves that pending on the levels whose passes take the list
+  // (k_gsrb4, k_resid_restrict, the box sums): the mean joins the context's
+  // list (omg_ctx::d_rhs_pend, written by k_mean on the stream), the level
+  // counts it (rhs_pend: the list's last rhs_pend entries, rhs_n - rhs_pend
+  // .. rhs_n - 1), and every pass subtracts the level's part of the list from
+  // the rhs values it loads, in order: ((rhs - M1) - M2) - ..., the bits the
+  // stored value would have had.  The cycle that finds the list full writes
+  // it out with its own mean (the storing form of the sums kernel).  Anything
+  // else that reads or writes rhs has the shifts written out first.  One
+  // rank only: a split level's deep-halo proxies hold rhs as well and every
+  // rank would have to decide alike; multi-rank runs subtract at once.
+  // rhs_pend_off: a reader that takes no list had to write the shifts out
+  // during a stand-alone cycle, so the level's cycles subtract at once until
+  // the smoothing counts, the smoother or the operator change.
+  int rhs_pend = 0;
+  bool rhs_pend_off = false;
+  // 5. Three caches that their inputs' writers drop: the refinement-boundary
+  // coarse parts in d_rbgv (valid while the level below is unchanged), rhs in
+  // ring order in d_rhs_lex, and the deep-halo proxies' rhs (both dropped by
+  // every writer of the level's rhs).
+  bool rbgv_ok = false;
+  bool rhs_lex_ok = false;
+  bool prox_rhs_ok = false;
+  // ---------------------------------------------------------------------
   bool has_rb = false, has_remote = false, has_phys = false;
   // the same flags over the level's boxes on EVERY rank (from the global
   // tree): decisions that choose collective calls use these, never the local
@@ -240,25 +300,6 @@ struct Level {
   bool any_rbx = false;
   bool all_parents = false;      // every box of this rank at this level is a parent
   bool prolong_smooth_ok = false;  // k_prolong_smooth can serve this level (see build_plan)
-  bool shift_pending = false;    // phi -= mean still to apply (see subtract_mean)
-  // rhs -= mean still to apply: the last rhs_pend entries of the context's
-  // list (omg_ctx::d_rhs_pend, entries rhs_n - rhs_pend .. rhs_n - 1), in
-  // that order (materialize_rhs)
-  int rhs_pend = 0;
-  // a reader that takes no list had to write the shifts out during a
-  // stand-alone cycle: the level's cycles subtract at once (today's pass)
-  // until the smoothing counts, the smoother or the operator change
-  bool rhs_pend_off = false;
-  // res of this level is still to store (materialize_res, omg_cycle.cpp): a
-  // stand-alone cycle's update_coarse ran its residual without the store, and
-  // res_src is the phi buffer (d_data or d_phi_buf) that launch read, ghost
-  // faces included; it stays unwritten until the res is stored or dropped
-  bool res_pend = false;
-  double* res_src = nullptr;
-  // a pass of a stand-alone cycle had to store the res before writing that
-  // buffer: the level's cycles store at once until the smoothing counts, the
-  // smoother or the operator change
-  bool res_pend_off = false;
   int8_t* d_nbk = nullptr;
   int* d_nba = nullptr;
   int* d_sendpos = nullptr;
@@ -278,9 +319,8 @@ struct Level {
   int* d_leaves = nullptr;
   uint8_t* d_parmask = nullptr;     // per box: 1 = a parent (k_fill_crhs)
   // refinement-boundary levels (one GPU): the coarse part of every rb ghost,
-  // [box][face][nc*nc] (RbSide::gv), valid while the level below is unchanged
+  // [box][face][nc*nc] (RbSide::gv), valid while rbgv_ok
   double* d_rbgv = nullptr;
-  bool rbgv_ok = false;
   // restriction onto this level from lvl+1 happens per fine box: for each of my
   // boxes at this level, the parent (local idx at lvl-1, or -1 if remote) and
   // its child offset inside the parent.
@@ -300,7 +340,6 @@ struct Level {
                         // lvl-1, coarse-side nb, child offset; recv: box*6+nb of my fine face)
   double* d_scratch_rhs = nullptr;   // leaf sums of rhs for the next get_sum
   double* d_rhs_lex = nullptr;       // rhs in ring order for the lexicographic smoother (ensure_rhs_lex)
-  bool rhs_lex_ok = false;           // d_rhs_lex equals rhs (dropped by every rhs writer)
   double* d_xlay = nullptr;          // x boundary layers of the last register-ring sweep (k_fill_tile_xl)
   // the second ghost-face set of phi for chains of register-ring sweeps (6
   // faces per box, the stored face layout; GhostSets in omg_kernels.h)
@@ -330,7 +369,6 @@ struct Level {
   int n_prox = 0;
   std::vector<int> prox_ids;     // global ids of the proxies, ascending
   Transfer deep_phi, deep_rhs;   // items: (box or n + proxy, brick)
-  bool prox_rhs_ok = false;      // the proxies' rhs equals the owners' rhs
   bool faces_pending = false;    // deep_after's remote faces still in flight on the comm stream
   int* d_physbox = nullptr;          // boxes with a physical face (k_phys_gc after such a chain)
   int n_physbox = 0;
@@ -449,12 +487,16 @@ struct omg_ctx {
   std::map<int, std::vector<int>> h_face_type_lvl[omg::kMaxVars];
   // scalars
   double* d_red = nullptr;             // device reductions (get_sum / subtract_mean)
-  // the rhs means of the last rhs_n stand-alone cycles, in order (k_mean
-  // writes each one here; they never visit the host), kRhsPendMax + 1 doubles:
-  // the cycle that writes the list out appends its own mean first
+  // The context's part of the lazy state (see Level, omg_lazy.cpp).
+  // d_rhs_pend: the rhs means of the last rhs_n stand-alone cycles, in order
+  // (k_mean writes each one here; they never visit the host), kRhsPendMax + 1
+  // doubles: the cycle that writes the list out appends its own mean first
   double* d_rhs_pend = nullptr;
   int rhs_n = 0;
   bool in_full_cycle = false;          // inside a stand-alone cycle over the whole tree (fas_vcycle)
+  bool phi_shift_pending = false;      // some level has shift_pending
+  bool phi_mean_on_side = false;       // its mean is still on the side stream (phi_mean_ready)
+  bool rhs_cache_valid = false;        // red acc of rhs is the sum of the current rhs
   bool no_rhs_pend = false;            // OMG_NO_RHS_PEND: every cycle writes rhs - mean at once
   bool no_res_pend = false;            // OMG_NO_RES_PEND: update_coarse always stores the level's res
   hipStream_t stream2 = nullptr;       // side stream (rhs sum chain)
@@ -465,7 +507,6 @@ struct omg_ctx {
   hipEvent_t ev_dense_in = nullptr, ev_dense_out = nullptr;   // omg_put_dense / omg_get_dense: the caller's stream
   long long dense_age = 0;
   std::vector<omg::BoxPlan> box_plans;   // lists of omg_put_boxes / omg_get_boxes (at most kBoxPlans)
-  bool phi_mean_on_side = false;
   bool no_tail = false;                // OMG_NO_TAIL: level-by-level coarse end (A/B checks)
   bool no_fuse_up = false;             // OMG_NO_FUSE_UP: separate prolongation and first up-substep
   bool no_skip1 = false;               // OMG_NO_SKIP1: correct colour 1 before the up-smoothing too
@@ -491,8 +532,6 @@ struct omg_ctx {
   int b3_min_boxes = omg::kB3MinBoxes;  // smallest level for k_gsrb3 (OMG_BLOCK3_MIN_BOXES, tests)
   int b3_col_small = 2;                // column length on levels below kB3MinBoxes (OMG_BLOCK3_SMALL_COL)
   int b3_col = 0;                      // k_gsrb3 column length (0: by level size; OMG_BLOCK3_COLUMN, tests)
-  bool rhs_cache_valid = false;        // red acc of rhs is the sum of the current rhs
-  bool phi_shift_pending = false;      // some level has shift_pending
   double* d_scalar = nullptr;          // small device scratch
   unsigned long long* d_maxslots = nullptr;   // launch_max slots (kept zeroed)
   // arguments of the coarse-tail kernel in device memory (a by-value kernel

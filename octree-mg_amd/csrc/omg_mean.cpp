@@ -1,7 +1,6 @@
 // omg_mean.cpp — get_sum / subtract_mean for periodic problems: the leaf
-// sums and the mean on the device, the pending phi shift and the pending rhs
-// shifts a stand-alone cycle leaves behind, and what every entry point does
-// about them (enter).
+// sums and the mean on the device.  What a stand-alone cycle's subtract_mean
+// leaves pending (the phi shift, the rhs shifts) is kept by omg_lazy.cpp.
 #include <algorithm>
 
 #include "omg_host.h"
@@ -65,7 +64,7 @@ static double subtract_volume(omg_ctx* c) {
 
 // MPI_Allreduce(acc) / volume into red_mean(ch), without leaving the stream
 // (RCCL all-gather + k_mean); the loopback transport gathers on the host.
-static void mean_device(omg_ctx* c, int ch, double* mean) {
+void mean_device(omg_ctx* c, int ch, double* mean) {
   const int n = c->n_ranks;
   if (n > 64) throw OmgError("subtract_mean: more than 64 ranks");
   double* all = red_all(c, ch);
@@ -89,100 +88,6 @@ double get_sum(omg_ctx* c, int iv) {
   HIPCHK(hipMemcpyAsync(c->h_scalar + 2, red_acc(c, kChPhi), 8, hipMemcpyDeviceToHost, c->stream));
   host_sync(c, c->stream);
   return allreduce(c, c->h_scalar[2], false);
-}
-
-// The phi mean of a stand-alone cycle's subtract_mean is finished on the side
-// stream (its chain overlaps the next cycle's rhs work); consumers wait here.
-void phi_mean_ready(omg_ctx* c) {
-  if (!c->phi_mean_on_side) return;
-  c->phi_mean_on_side = false;
-  HIPCHK(hipStreamWaitEvent(c->stream, c->ev_phi, 0));
-  if (c->n_ranks > 1) mean_device(c, kChPhi, red_mean(c, kChPhi));
-}
-
-// A pending phi -= mean (left by a standalone V-cycle, see subtract_mean) is
-// applied before anything else reads phi.
-void materialize_level(omg_ctx* c, Level* L) {
-  if (!L->shift_pending) return;
-  res_before_write(c, L, L->d_phi);
-  phi_mean_ready(c);
-  L->shift_pending = false;
-  rb_stale_above(c, L->lvl);
-  if (L->n) {
-    Prof p(c, "subtract", (double)L->n * L->nc * L->nc * L->nc, L->lvl);
-    launch_subtract(L->view(), 1, red_mean(c, kChPhi), 1, c->stream);
-  }
-}
-void materialize_phi(omg_ctx* c) {
-  if (!c->phi_shift_pending) return;
-  for (auto& kv : c->levels) materialize_level(c, &kv.second);
-  c->phi_shift_pending = false;
-}
-
-// Pending rhs shifts.  mg_fas_vcycle begins every periodic cycle with
-// rhs <- rhs - mean(rhs) (m_multigrid.f90:245-276).  A stand-alone cycle
-// leaves that pending on the levels whose passes take the list (k_gsrb4,
-// k_resid_restrict, the box sums): the mean joins the context's list
-// (d_rhs_pend, written by k_mean on the stream), the level counts it
-// (Level::rhs_pend), and every pass subtracts the level's part of the list
-// from the rhs values it loads, in order: ((rhs - M1) - M2) - ..., the bits
-// the stored value would have had.  The cycle that finds the list full writes
-// it out with its own mean (the storing form of the sums kernel).  Anything
-// else that reads or writes rhs writes the shifts out first (materialize_rhs:
-// enter() for the entry points, the other readers inside a cycle themselves).
-// One rank only: a split level's deep-halo proxies hold rhs as well and every
-// rank would have to decide alike; multi-rank runs subtract at once, as before.
-RhsShifts rhs_shifts(omg_ctx* c, const Level* L) {
-  RhsShifts r;
-  r.s = c->d_rhs_pend + (c->rhs_n - L->rhs_pend);
-  r.n = L->rhs_pend;
-  return r;
-}
-// The stored values catch up with the list; the box sums in the level's
-// scratch and the chained sum are those of the same values and stay valid.
-void materialize_rhs(omg_ctx* c, Level* L) {
-  if (!L->rhs_pend) return;
-  // inside a stand-alone cycle: a reader that takes no list ran on this level
-  if (c->in_full_cycle) L->rhs_pend_off = true;
-  {
-    Prof p(c, "subtract_rhs", (double)L->n * L->nc * L->nc * L->nc, L->lvl);
-    launch_subtract_sums(L->sweep_view(), 2, L->d_leaves, L->n, rhs_shifts(c, L), nullptr, c->stream);
-  }
-  L->rhs_pend = 0;
-  L->rhs_lex_ok = L->prox_rhs_ok = false;
-}
-void materialize_rhs_all(omg_ctx* c) {
-  for (auto& kv : c->levels) materialize_rhs(c, &kv.second);
-}
-void rhs_pend_retry(omg_ctx* c) {
-  for (auto& kv : c->levels) kv.second.rhs_pend_off = kv.second.res_pend_off = false;
-}
-// whether a cycle may leave the level's rhs - mean pending: its passes are
-// the block passes that take the list
-static bool rhs_pend_ok(omg_ctx* c, const Level* L) {
-  return c->n_ranks == 1 && c->smoother == OMG_SMOOTHER_GSRB && !c->no_rhs_pend && L->d_b3 && !L->b3_phys &&
-         !L->rhs_pend_off;
-}
-
-// the ring-order rhs copies: every write of a level's rhs drops its copy
-void drop_rhs_lex(omg_ctx* c) {
-  for (auto& kv : c->levels) kv.second.rhs_lex_ok = kv.second.prox_rhs_ok = false;
-}
-static void drop_rhs_cache(omg_ctx* c) {
-  c->rhs_cache_valid = false;
-  drop_rhs_lex(c);
-}
-// entry points other than the cycles: apply pending phi work first; `writes`
-// = the call may change rhs (the cached rhs sum is dropped)
-void enter(omg_ctx* c, bool writes) {
-  // (a pending res first: it is formed from phi and rhs as they stand, the
-  // shifts below subtract in place)
-  materialize_res_all(c);
-  materialize_rhs_all(c);
-  materialize_phi(c);
-  for (auto& kv : c->levels)
-    if (kv.second.gc_deferred) fill_gc_lvl(c, kv.first, 1);
-  if (writes) drop_rhs_cache(c);
 }
 
 // subtract_mean (m_multigrid.f90:245-276), mean computed on the device.
@@ -256,7 +161,7 @@ void subtract_mean(omg_ctx* c, int iv, int ghosts, int mode) {
           L->rhs_pend = 0;
         }
       } else {
-        materialize_rhs(c, L);   // (never pending here: such a level's cycles subtract at once)
+        ready(c, l, kRhs);   // (never pending here: such a level's cycles subtract at once)
         Prof p(c, "subtract_rhs", cells, l);
         launch_subtract(L->view(), 2, mean, 0, c->stream);
         if (l >= 1 && !L->leaves.empty()) all_fused = false;

@@ -19,7 +19,8 @@ b. counts changed between cycles, every stored cell of phi, rhs, old and res
    readers of phi's ghosts;
 c. the coarse solve's cap and relative tolerance changed between cycles, on a
    tree whose coarse levels run in the single-workgroup tail and on one whose
-   coarse solve runs level by level from the host (vlpl).
+   coarse solve runs level by level from the host (vlpl);
+d. the launches of the top level in the steady state of back-to-back cycles.
 
 Every comparison is bitwise."""
 import json
@@ -205,3 +206,35 @@ def test_coarse_limits_changed_between_cycles(tree, limit):
     p.run([V1, V0])
     p.set(coarse=limit)
     p.run([V1])
+
+
+# -- d. the steady state of back-to-back cycles --------------------------------
+STEADY = {"subtract": 0, "fill_gc": 0, "residual": 0, "smoother_gsrb": 0, "smoother_gsrb4": 1,
+          "smoother_gsrb4p": 1, "resid_restrict": 1}
+
+
+def test_steady_state_launches_on_the_top_level(monkeypatch):
+    """Stand-alone cycles at (2, 2) without the max residual, back to back:
+    from the third on, everything a cycle leaves unwritten (the phi mean, the
+    rhs shifts, the top level's res and ghost faces) is taken up by the next
+    cycle's own passes, so the top level sees one k_gsrb4 down pass, one
+    residual + restriction and one k_gsrb4 correction pass per cycle, and
+    no launch that writes any of it out."""
+    _set_bound(monkeypatch, "64")
+    cfg = parse(PER128)
+    cfg["cycles"] = (2, 2)
+    dev = DeviceBackend(cfg)
+    setup_problem(dev)
+    ctx = dev.mg.ctx
+    for _ in range(2):
+        dev.vcycle(False)
+    ctx.call("synchronize")
+    ctx.call("set_profiling", 1)
+    top = dev.tree.highest_lvl
+    for cycle in (3, 4):
+        ctx.call("reset_stats")
+        dev.vcycle(False)
+        ctx.call("synchronize")
+        n = {f: ctx.kernel_stats(f"{f}@{top}")[0] for f in STEADY}
+        print("cycle", cycle, n)
+        assert n == STEADY, (cycle, n)
