@@ -327,6 +327,68 @@ int omg_get_boxes(omg_ctx *ctx, int iv, int n_boxes, const int *ids, double *dev
                   const long long *box_off, const long long stride[3], int ghost, int fill,
                   void *stream, long long *n_cells);
 
+/* The gradient of variable iv in block layout, in DEVICE memory: what a
+ * block-AMR host computes after a solve (E = -grad phi, or the projection
+ * B -= grad phi) from the blocks that mg_copy_from_tree_gc
+ * (coupling_amrvac/mod_multigrid_coupling.t:236-267) hands it, here in one
+ * pass from the stored boxes and their face ghosts, with no copy of the boxes
+ * in between.  ids, box_off, stride, stream, the plan-only behaviour and the
+ * ownership, range and "listed twice" checks are exactly omg_get_boxes's;
+ * box_off[q] is the offset of interior cell (1,1,1) of box q and is shared by
+ * the three component pools.  dev[d] is the pool of component d (0 x, 1 y,
+ * 2 z); a NULL dev[d] skips that component.  Pools may interleave (the
+ * slices [:, d] of one [n, 3, m, m, m] pool), as for omg_put_boxes.
+ * With o(i,j,k) = box_off[q] + (i-1) + (j-1)*stride[1] + (k-1)*stride[2]:
+ * centering == 0, cell-centred: for 1 <= i,j,k <= nc
+ *     dev[d][o(i,j,k)] = (cc(+1 in d) - cc(-1 in d)) * f_d,
+ *     f_d = (0.5 * scale) / dr_d,
+ * omg_get_dense_grad's definition, rounding and signed zeros; stride[1] >= m
+ * and stride[2] >= stride[1]*m with m = nc_max.
+ * centering == 1, face-centred: for the index along d from 0 to nc and the
+ * two other indices from 1 to nc
+ *     dev[d][o(i,j,k)] = (cc(+1 in d) - cc(i,j,k)) * f_d,   f_d = scale / dr_d,
+ * the difference across the face between the cells i and i+1 (along d) at
+ * cell i's slot: a staggered array whose index i holds face i+1/2, so the
+ * face 0 lies one element (d = 0), row (d = 1) or plane (d = 2) below the
+ * interior; m = nc_max + 1 in the stride rule.
+ * f_d is computed on the host in double with the dr of each box's level (a
+ * list mixes levels): one subtraction and one multiplication per value, no
+ * contraction.  cc is the stored box with its six face ghosts; the
+ * refinement-boundary ghosts of a fill are the interpolation from the coarse
+ * neighbour, so the differences over a leaf and its filled ghosts are the
+ * composite gradient of the reference's users.  Edge and corner ghosts are
+ * never read; pool elements outside the values named keep their bits, boxes
+ * not listed keep theirs.
+ * *n_cells (if non-NULL) = the values per component, counted on the host: sum
+ * of nc^3, or of (nc+1)*nc^2 for face centring.
+ * fill and state: exactly omg_get_boxes's (pending work is applied, deferred
+ * ghosts are filled and a pending res is formed before anything is read;
+ * fill != 0 fills iv on every level first and is collective on several ranks,
+ * fill == 0 uses the ghosts as they stand; on a replicated level only the
+ * host's own boxes are accepted; a cycle after the call gives the bits it
+ * would have given without it).
+ * Errors (nothing is launched, no state is touched): those of omg_get_boxes,
+ * each non-NULL pool checked as its dev is, from the first to the last
+ * touched element of the centring; a centering other than 0 or 1; all three
+ * pointers NULL with n_boxes > 0; two non-NULL pointers that are equal.
+ * The call shares the context's cache of four lists with omg_put_boxes /
+ * omg_get_boxes (the same records; the centring is part of the key, "16-B
+ * aligned" is true when every non-NULL base is): a cached list uploads
+ * nothing and never waits on the host.
+ * Kernels: a tile kernel for 16^3 and 8^3 boxes (16-B stores when every
+ * base, box_off and stride is even, 8-B stores otherwise), a per-cell kernel
+ * for every other size and where it measured faster: for a level of which
+ * fewer than 512 (face centring) or 1536 (cell centring) boxes are listed,
+ * and for cell centring into rows with a gap between them (stride[1] > nc)
+ * of more than 2048 * 16^3 cells; both give the same bits.
+ * OMG_BOXES_GENERIC=1 and OMG_BOXES_TILE=1 apply as they do to omg_get_boxes.
+ * Profiling families: boxes_grad (the call), boxes_grad_tile (the tile
+ * kernel, per level). */
+int omg_get_boxes_grad(omg_ctx *ctx, int iv, int n_boxes, const int *ids,
+                       double *const dev[3], const long long *box_off,
+                       const long long stride[3], double scale, int centering,
+                       int fill, void *stream, long long *n_cells);
+
 /* The hot path.  omg_fas_vcycle = mg_fas_vcycle (src/m_multigrid.f90:150-243);
  * highest_lvl < lowest_lvl means "not present".  omg_fas_fmg = mg_fas_fmg
  * (:84-147).  max_res is written when want_max_res (the optional argument). */

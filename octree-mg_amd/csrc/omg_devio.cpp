@@ -1,7 +1,8 @@
 // omg_devio.cpp — device I/O: omg_put_dense / omg_get_dense (windows of a
 // level's cell grid, kernels in omg_dense.hip), omg_get_dense_grad (the same
-// windows of a gradient, omg_dense_grad.hip) and omg_put_boxes / omg_get_boxes
-// (block lists, omg_boxes.hip): the caller's device memory, in the order of
+// windows of a gradient, omg_dense_grad.hip), omg_put_boxes / omg_get_boxes
+// (block lists, omg_boxes.hip) and omg_get_boxes_grad (the same lists of a
+// gradient, omg_boxes_grad.hip): the caller's device memory, in the order of
 // the caller's stream, by cached records.  What the entries share stands first.
 #include <algorithm>
 
@@ -341,8 +342,10 @@ static void boxes_build(omg_ctx* c, BoxPlan& P, int n_boxes, const int* ids, con
     P.recs[G.first + G.n++] = BoxRec{c->local_index[id], lvl, box_off[q]};
     if (!P.aligned || (box_off[q] | P.stride[1] | P.stride[2]) & 1) G.odd = true;
     const long long nc = L->nc;
-    P.n_cells += nc * nc * nc + (long long)P.ghost * 6 * nc * nc;
+    // (a face-centred gradient: nc + 1 faces along the component's direction)
+    P.n_cells += P.centering == 1 ? (nc + 1) * nc * nc : nc * nc * nc + (long long)P.ghost * 6 * nc * nc;
     // first and last touched element: (1,1,0) and (nc,nc,nc+1) with ghosts
+    // (a face-centred component starts one stride[d] lower: boxes_grad)
     const long long lo = box_off[q] - (P.ghost ? P.stride[2] : 0);
     const long long hi = box_off[q] + (nc - 1) + (nc - 1) * P.stride[1] + (nc - 1 + P.ghost) * P.stride[2];
     P.lo_ext = have_ext ? std::min(P.lo_ext, lo) : lo;
@@ -351,16 +354,50 @@ static void boxes_build(omg_ctx* c, BoxPlan& P, int n_boxes, const int* ids, con
   }
 }
 
-void box_io(omg_ctx* c, int iv, int n_boxes, const int* ids, double* dev, const long long* box_off,
-            const long long* stride, int ghost, bool fill, void* stream, long long* n_cells, bool put) {
-  const Fail fail{put ? "omg_put_boxes" : "omg_get_boxes"};
-  if (iv < 1 || iv > c->n_vars) fail("bad variable index");
-  if (ghost != 0 && ghost != 1) fail("ghost must be 0 or 1");
+// The checks of a list's arguments that the block entries share.
+static void boxes_check_list(int n_boxes, const int* ids, const long long* box_off, const long long* stride,
+                             const Fail& fail) {
   if (n_boxes < 0) fail("negative n_boxes");
   if (!stride) fail("stride is required");
   if (stride[0] != 1) fail("stride[0] must be 1");
   if (stride[1] < 1 || stride[2] < 1 || stride[1] > kDenseMax || stride[2] > kDenseMax) fail("stride out of range");
   if (n_boxes > 0 && (!ids || !box_off)) fail("NULL ids or box_off with n_boxes > 0");
+}
+
+// The cached records of a list, or null (a cached list was checked when it
+// was built).  centering: kBoxCopy for the copies, else omg_get_boxes_grad's.
+static BoxPlan* boxes_cached(omg_ctx* c, int n_boxes, const int* ids, const long long* box_off,
+                             const long long* stride, int ghost, int centering, bool aligned) {
+  BoxPlan* P = nullptr;
+  for (auto& Q : c->box_plans)
+    if ((int)Q.ids.size() == n_boxes && Q.ghost == ghost && Q.centering == centering &&
+        std::equal(stride, stride + 3, Q.stride) && Q.aligned == aligned &&
+        std::equal(ids, ids + n_boxes, Q.ids.begin()) && std::equal(box_off, box_off + n_boxes, Q.off.begin()))
+      P = &Q;
+  return P;
+}
+
+// The cache slot of a call's list, the most recently used from now on: the
+// cached one, or `fresh` in a new or the oldest slot with its records on
+// their way to the device.
+static BoxPlan& boxes_claim(omg_ctx* c, BoxPlan* cached, BoxPlan& fresh) {
+  BoxPlan& S = take_slot(c, c->box_plans, kBoxPlans, cached);
+  if (!cached) {
+    // (the slot keeps its buffers and its place in the order of use)
+    fresh.buf = S.buf;
+    fresh.age = S.age;
+    S = std::move(fresh);
+    S.buf.upload(c, S.recs);
+  }
+  return S;
+}
+
+void box_io(omg_ctx* c, int iv, int n_boxes, const int* ids, double* dev, const long long* box_off,
+            const long long* stride, int ghost, bool fill, void* stream, long long* n_cells, bool put) {
+  const Fail fail{put ? "omg_put_boxes" : "omg_get_boxes"};
+  if (iv < 1 || iv > c->n_vars) fail("bad variable index");
+  if (ghost != 0 && ghost != 1) fail("ghost must be 0 or 1");
+  boxes_check_list(n_boxes, ids, box_off, stride, fail);
   if (n_boxes > 0 && !dev) fail("NULL pointer with n_boxes > 0");
   if (c->levels.empty()) fail("no tree (omg_tree_setup)");
   // (the switches choose the kernel at launch: the records do not depend on them)
@@ -368,12 +405,7 @@ void box_io(omg_ctx* c, int iv, int n_boxes, const int* ids, double* dev, const 
   const bool odd8 = boxes_odd8(put, ghost);
   const bool aligned = ((uintptr_t)dev & 15) == 0;
   // a cached list was checked when it was built
-  BoxPlan* P = nullptr;
-  for (auto& Q : c->box_plans)
-    if ((int)Q.ids.size() == n_boxes && Q.ghost == ghost && std::equal(stride, stride + 3, Q.stride) &&
-        Q.aligned == aligned && std::equal(ids, ids + n_boxes, Q.ids.begin()) &&
-        std::equal(box_off, box_off + n_boxes, Q.off.begin()))
-      P = &Q;
+  BoxPlan* P = boxes_cached(c, n_boxes, ids, box_off, stride, ghost, kBoxCopy, aligned);
   BoxPlan fresh;
   if (P) {
     for (int q = 0; q < n_boxes && put && P->any_replicated; q++)   // (refused again: a put)
@@ -410,14 +442,7 @@ void box_io(omg_ctx* c, int iv, int n_boxes, const int* ids, double* dev, const 
   }
   if (n_cells) *n_cells = R.n_cells;
   if (n_boxes == 0) return;
-  BoxPlan& S = take_slot(c, c->box_plans, kBoxPlans, P);
-  if (!P) {
-    // (the slot keeps its buffers and its place in the order of use)
-    fresh.buf = S.buf;
-    fresh.age = S.age;
-    S = std::move(fresh);
-    S.buf.upload(c, S.recs);
-  }
+  BoxPlan& S = boxes_claim(c, P, fresh);
   join_in(c, stream);
   {
     Prof p(c, put ? "boxes_put" : "boxes_get", (double)S.n_cells);
@@ -435,6 +460,98 @@ void box_io(omg_ctx* c, int iv, int n_boxes, const int* ids, double* dev, const 
                           c->stream);
       } else {
         launch_boxes_cell(V, iv, S.buf.d + G.first, G.n, dev, stride[1], stride[2], ghost, put, c->stream);
+      }
+    }
+    HIPCHK(hipGetLastError());
+  }
+  join_out(c, stream);
+}
+
+// What tools/box_grad_bench.py measured for this entry's kernels (DESIGN §19,
+// 16^3 boxes, listed boxes of one level): one workgroup per box leaves the
+// GPU short of work on short lists here too.  Face centring: the per-cell
+// kernel won at 256 boxes, the tile kernel from 512 on.  Cell centring: the
+// per-cell kernel won up to 512 boxes and tied at 1024, the tile kernel won
+// from 1536 on into whole rows (stride[1] == nc); into rows with a gap
+// between them it won at 1536 and 2048 boxes only, the per-cell kernel from
+// 3072 on, where both write partial lines.
+constexpr int kBoxesGradTileMinFace = 512;
+constexpr int kBoxesGradTileMinCell = 1536;
+constexpr long long kBoxesGradGapCells = 2048LL * 4096;
+
+// omg_get_boxes_grad: omg_get_boxes's list, records, cache and stream
+// ordering; up to three component pools that share box_off and the strides.
+void boxes_grad(omg_ctx* c, int iv, int n_boxes, const int* ids, double* const* dev, const long long* box_off,
+                const long long* stride, double scale, int centering, bool fill, void* stream, long long* n_cells) {
+  const Fail fail{"omg_get_boxes_grad"};
+  if (iv < 1 || iv > c->n_vars) fail("bad variable index");
+  if (centering != 0 && centering != 1) fail("centering must be 0 (cells) or 1 (faces)");
+  boxes_check_list(n_boxes, ids, box_off, stride, fail);
+  if (!dev) fail("the array of component pointers is required");
+  bool aligned = true, any = false;
+  for (int d = 0; d < 3; d++)
+    if (dev[d]) {
+      any = true;
+      aligned = aligned && ((uintptr_t)dev[d] & 15) == 0;
+      for (int e = 0; e < d; e++)
+        if (dev[e] == dev[d])
+          fail("components " + std::to_string(e) + " and " + std::to_string(d) + " share one pointer");
+    }
+  if (n_boxes > 0 && !any) fail("NULL pointers for all three components with n_boxes > 0");
+  if (c->levels.empty()) fail("no tree (omg_tree_setup)");
+  const bool generic = env_flag("OMG_BOXES_GENERIC"), force_tile = env_flag("OMG_BOXES_TILE");
+  BoxPlan* P = boxes_cached(c, n_boxes, ids, box_off, stride, 0, centering, aligned);
+  BoxPlan fresh;
+  if (!P) {
+    fresh.centering = centering;
+    std::copy(stride, stride + 3, fresh.stride);
+    fresh.aligned = aligned;
+    boxes_build(c, fresh, n_boxes, ids, box_off, false, fail);
+  }
+  const BoxPlan& R = P ? *P : fresh;
+  if (n_boxes > 0) {
+    const long long m = R.nc_max + centering;
+    if (stride[1] < m) fail(centering ? "stride[1] < nc + 1" : "stride[1] < nc");
+    if (stride[2] / m < stride[1]) fail(centering ? "stride[2] < stride[1]*(nc + 1)" : "stride[2] < stride[1]*nc");
+  }
+  if (c->host_only) {
+    if (n_cells) *n_cells = R.n_cells;
+    return;
+  }
+  if (n_boxes > 0) {
+    // (a face-centred component starts one element, row or plane below its boxes' interiors)
+    for (int d = 0; d < 3; d++)
+      if (dev[d]) check_device_range(c, dev[d], R.lo_ext - (centering ? stride[d] : 0), R.hi_ext, "a block", fail);
+    for (const BoxGroup& G : R.groups)
+      if ((long long)G.n * 16 > INT_MAX) fail("too many boxes for one launch");
+  }
+  // --- nothing of the state was touched up to here
+  enter_get(c, iv, fill, c->lowest, c->highest);
+  if (n_cells) *n_cells = R.n_cells;
+  if (n_boxes == 0) return;
+  BoxPlan& S = boxes_claim(c, P, fresh);
+  join_in(c, stream);
+  {
+    Prof p(c, "boxes_grad", (double)S.n_cells);
+    for (const BoxGroup& G : S.groups) {
+      const Level* L = level_ptr(c, G.lvl);
+      const LevelView V = L->view();
+      DenseGrad A;
+      for (int d = 0; d < 3; d++) {
+        A.out[d] = dev[d];
+        A.f[d] = (centering ? scale : 0.5 * scale) / L->dr[d];
+      }
+      const bool measured =
+          centering ? G.n >= kBoxesGradTileMinFace
+                    : G.n >= kBoxesGradTileMinCell &&
+                          (stride[1] == L->nc || (long long)G.n * L->nc * L->nc * L->nc <= kBoxesGradGapCells);
+      const bool tile = !generic && boxes_tile_nc(L->nc) && (force_tile || measured);
+      if (tile) {
+        Prof pr(c, "boxes_grad_tile", (double)G.n * (L->nc + centering) * L->nc * L->nc, G.lvl);
+        launch_boxes_grad_tile(V, iv, S.buf.d + G.first, G.n, A, stride[1], stride[2], centering != 0, G.odd,
+                               c->stream);
+      } else {
+        launch_boxes_grad_cell(V, iv, S.buf.d + G.first, G.n, A, stride[1], stride[2], centering != 0, c->stream);
       }
     }
     HIPCHK(hipGetLastError());

@@ -190,13 +190,15 @@ struct BoxGroup {
   int lvl = 0, first = 0, n = 0;
   bool odd = false;    // some row of some block is not 16-B aligned
 };
+constexpr int kBoxCopy = -1;        // BoxPlan::centering of omg_put_boxes / omg_get_boxes
 struct BoxPlan {
-  // the key: the list by value, the strides, ghost and whether the base is
-  // 16-B aligned
+  // the key: the list by value, the strides, ghost, the centring and whether
+  // the base (omg_get_boxes_grad: every non-null base) is 16-B aligned
   std::vector<int> ids;
   std::vector<long long> off;
   long long stride[3] = {0, 0, 0};
   int ghost = 0;
+  int centering = kBoxCopy;         // omg_get_boxes_grad: 0 cell-, 1 face-centred values
   bool aligned = false;
   std::vector<BoxRec> recs;         // (grouped; uploaded through buf)
   std::vector<BoxGroup> groups;
@@ -506,7 +508,7 @@ struct omg_ctx {
   hipEvent_t ev_main = nullptr, ev_side = nullptr, ev_phi = nullptr;
   hipEvent_t ev_dense_in = nullptr, ev_dense_out = nullptr;   // omg_put_dense / omg_get_dense: the caller's stream
   long long dense_age = 0;
-  std::vector<omg::BoxPlan> box_plans;   // lists of omg_put_boxes / omg_get_boxes (at most kBoxPlans)
+  std::vector<omg::BoxPlan> box_plans;   // lists of the omg_*_boxes* entries (at most kBoxPlans)
   bool no_tail = false;                // OMG_NO_TAIL: level-by-level coarse end (A/B checks)
   bool no_fuse_up = false;             // OMG_NO_FUSE_UP: separate prolongation and first up-substep
   bool no_skip1 = false;               // OMG_NO_SKIP1: correct colour 1 before the up-smoothing too

@@ -217,6 +217,17 @@ void launch_dense_grad_tile(const LevelView& L, int iv, const DenseClip* clips, 
                             long long s1, long long s2, hipStream_t st);
 void launch_dense_grad_cell(const LevelView& L, int iv, const DenseClip* clips, int n, const DenseGrad& G,
                             long long s1, long long s2, hipStream_t st);
+// omg_get_boxes_grad (omg_boxes_grad.hip): the differences of variable iv over
+// the boxes of one level listed by records (BoxRec), into blocks of the
+// component pools G.out[d] (null: skipped) laid out as the blocks above.
+// face = false: (cc(+1 in d) - cc(-1 in d)) * G.f[d] at the interior cells;
+// face = true: (cc(+1 in d) - cc) * G.f[d] at the index 0 .. nc along d.  The
+// tile kernel takes boxes of boxes_tile_nc() sizes (w8: 8-B stores, for
+// blocks that are not 16-B aligned), the per-cell kernel any box.
+void launch_boxes_grad_tile(const LevelView& L, int iv, const BoxRec* recs, int n, const DenseGrad& G, long long s1,
+                            long long s2, bool face, bool w8, hipStream_t st);
+void launch_boxes_grad_cell(const LevelView& L, int iv, const BoxRec* recs, int n, const DenseGrad& G, long long s1,
+                            long long s2, bool face, hipStream_t st);
 void launch_phi_bc_store(const LevelView& L, const GcBC& bc, int* nba, hipStream_t st);
 
 // The coarse end of the V-cycle in ONE single-workgroup launch (omg_tiles.hip):

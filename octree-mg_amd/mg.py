@@ -306,6 +306,68 @@ class MG(MGTree):
                                    torch.cuda.current_stream(out.device).cuda_stream)
         return out, cells
 
+    def get_blocks_grad(self, ids, iv=1, out=None, ghost_width=0, scale=1.0, fill=True, centering="cell",
+                        components=(True, True, True)):
+        """omg_get_boxes_grad: the gradient of variable iv over the boxes `ids`
+        (as get_blocks lists them) in block layout.  `out` is a torch.float64
+        tensor [3, n, m, m, m] on the context's GPU (x, y, z components,
+        m = nc + 2 * ghost_width; default: torch.empty of that shape), or a
+        sequence of three tensors [n, m, m, m] or Nones of one shape and one
+        set of strides; the layout checks are set_blocks'.  A component that
+        is None or whose entry of `components` is false is skipped and its
+        tensor left untouched.
+        centering="cell": (cc(+1 in d) - cc(-1 in d)) * 0.5 * scale / dr_d at
+        the interior cells of each block (get_dense_grad's values).
+        centering="face" (ghost_width >= 1): (cc(+1 in d) - cc) * scale / dr_d
+        for the index along d from 0 to nc, face i at cell i's element, so
+        face 0 lies in the first ghost layer below the interior.
+        scale = -1.0: the field of a potential.  fill: the ghost cells of iv
+        are filled first on every level (collective on several ranks), so that
+        refinement-boundary ghosts carry the coarse neighbour's interpolation;
+        without it they are used as they stand.  Everything else of `out`
+        keeps its values.  Ordered on torch's current stream.  Returns
+        (out, values per component)."""
+        import torch
+        what = "get_blocks_grad"
+        if centering not in ("cell", "face"):
+            raise ValueError(f"{what}: centering {centering!r}, 'cell' or 'face' is required")
+        if len(components) != 3:
+            raise ValueError(f"{what}: components takes three flags")
+        if centering == "face" and int(ghost_width) < 1:
+            raise ValueError(f"{what}: centering='face' needs ghost_width >= 1")
+        if out is None:
+            self._require_alloc()
+            idl = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+            sizes = {int(self.box_size_lvl[int(l)]) for l in np.unique(self.lvl[idl])} if len(idl) else {0}
+            if len(sizes) > 1:
+                raise ValueError(f"{what}: the listed boxes have the box sizes {sorted(sizes)}, one is required")
+            m = sizes.pop() + 2 * int(ghost_width)
+            dev = self.ctx.device
+            out = torch.empty((3, len(idl), m, m, m), dtype=torch.float64,
+                              device=torch.device("cuda", dev if dev >= 0 else torch.cuda.current_device()))
+        if isinstance(out, torch.Tensor):
+            if out.dim() != 5 or out.shape[0] != 3:
+                raise ValueError(f"{what}: a torch tensor [3, box, k, j, i] is required")
+            parts = [out[d] for d in range(3)]
+        else:
+            parts = list(out)
+            if len(parts) != 3:
+                raise ValueError(f"{what}: three tensors (or None) are required")
+        parts = [t if components[d] else None for d, t in enumerate(parts)]
+        used = [t for t in parts if t is not None]
+        if not used:
+            raise ValueError(f"{what}: no component is asked for")
+        args = [self._blocks_args(t, ids, ghost_width, False, what) for t in used]
+        idl, off, stride, _ = args[0]
+        if any(t.shape != used[0].shape or t.stride() != used[0].stride() for t in used):
+            raise ValueError(f"{what}: the components differ in shape or strides")
+        if any(t.device != used[0].device for t in used):
+            raise ValueError(f"{what}: the components are on different devices")
+        cells = self.ctx.get_boxes_grad(iv, idl, [0 if t is None else t.data_ptr() for t in parts], off, stride,
+                                        scale, int(centering == "face"), fill,
+                                        torch.cuda.current_stream(used[0].device).cuda_stream)
+        return out, cells
+
     def _require_alloc(self):
         if not self.is_allocated:
             raise RuntimeError("allocate_storage: tree is not allocated")
