@@ -468,6 +468,19 @@ int omg_free_planes(omg_ctx *ctx, int *fft_lvl, int *nx, double *planes, long lo
 int omg_plan_transfer(omg_ctx *ctx, int lvl, int which, int dir, int cap, int *peers,
                       long long *keys, int *n_items, int *item_doubles);
 
+/* The tables the block passes (k_gsrb3 / k_gsrb4) read level lvl through, as
+ * built by omg_tree_setup: which 0 the column records (one per workgroup),
+ * which 1 the coarse records of the correction form (one per column); the
+ * layouts are described in octree-mg_amd/csrc/omg_kernels.h.  *n_cols records
+ * of *rec_ints ints each, 0 where the level has none; recs gets them all if it
+ * holds cap >= n_cols * rec_ints ints, else nothing (cap 0: the sizes only).
+ * Host copies: the call works on plan-only contexts and changes no state.  On
+ * a level split over ranks, the ranks agree on the coarse records after each
+ * has built its own (all use them or none); a plan-only context joins no such
+ * round and returns the ones it built. */
+int omg_plan_columns(omg_ctx *ctx, int lvl, int which, int cap, int *recs, int *n_cols,
+                     int *rec_ints);
+
 /* The context's communicator (no reference counterpart; mg%n_cpu of
  * mg_comm_init, src/m_communication.f90:14-35, as the transport sees it):
  * *n_ranks = the ranks it joins (ncclCommCount for RCCL), *transport = one of

@@ -317,6 +317,17 @@ int omg_plan_transfer(omg_ctx* c, int lvl, int which, int dir, int cap, int* pee
   });
 }
 
+int omg_plan_columns(omg_ctx* c, int lvl, int which, int cap, int* recs, int* n_cols, int* rec_ints) {
+  return guarded([&] {
+    const Level* L = level_ptr(c, lvl);
+    if (!L) throw OmgError("no such level");
+    if (which < 0 || which > 1) throw OmgError("omg_plan_columns: bad table");
+    const std::vector<int>& h = columns_host(*L, which, rec_ints);
+    *n_cols = (int)(h.size() / *rec_ints);
+    if (cap > 0 && (size_t)cap >= h.size()) std::copy(h.begin(), h.end(), recs);
+  });
+}
+
 int omg_set_operator(omg_ctx* c, int op, double lambda) {
   return guarded([&] { set_operator(c, op, lambda); });
 }

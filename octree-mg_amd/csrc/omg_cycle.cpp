@@ -679,7 +679,7 @@ static bool prolong_smooth(omg_ctx* c, int lvl) {
 // correct_children(l-1) + fill of l + up-smoothing substeps 1-3 of l in one
 // k_gsrb3 pass (its correct_children form); returns whether it ran (the caller
 // then starts smooth_boxes at substep 4).  Levels with k_gsrb3's coarse
-// records (build_block3c), whose coarse level has consistent ghosts (the
+// records (build_coarse_columns, omg_columns.cpp), whose coarse level has consistent ghosts (the
 // reference's correction reads the parents' ghost cells; the pass reads the
 // neighbour parents' cells).
 static bool block3c_ok(omg_ctx* c, const Level* F) {

@@ -245,8 +245,15 @@ void finalize_transfer(Transfer& T);
 void rbh_build(omg_ctx* c);
 void ensure_rhs_lex(omg_ctx* c);
 void free_levels(omg_ctx* c);
-bool b3_usable(omg_ctx* c, int lvl, B3Phys& P, const B3Phys*& ph);
 void build_plan(omg_ctx* c);
+
+// --- omg_columns.cpp: the block passes' column and coarse records
+void build_columns(omg_ctx* c, Level& L);
+void build_coarse_columns(omg_ctx* c, Level& F, const Level& C);
+void agree_columns(omg_ctx* c);
+bool b3_usable(omg_ctx* c, int lvl, B3Phys& P, const B3Phys*& ph);
+// (which 0: the column records, 1: the coarse records; empty: the level has none)
+const std::vector<int>& columns_host(const Level& L, int which, int* rec_ints);
 
 // --- omg_lazy.cpp: the lazy per-level state (omg_internal.h, above Level's
 // lazy fields).  What a pass on a level reads and writes: ready() before its

@@ -352,17 +352,18 @@ struct Level {
   double* d_phi_buf = nullptr;
   int* d_b3 = nullptr;
   int n_b3 = 0;
-  std::vector<int> h_b3;   // (host copy, for the coarse records below)
+  std::vector<int> h_b3;   // (host copy, in plan-only contexts too: omg_plan_columns)
   // some columns have physical faces (round 6): the passes take the ghosts
-  // there from constant boundary values (b3_phys, omg_plan.cpp)
+  // there from constant boundary values (b3_phys, omg_columns.cpp)
   bool b3_phys = false;
   // k_gsrb3's correct_children form: per column the coarse boxes around it
   // (launch_gsrb3's ccols); null: the level's up-smoothing starts with
   // k_prolong_smooth
   int* d_b3c = nullptr;
+  std::vector<int> h_b3c;   // (host copy)
   // Deep halo (k_gsrb3 / k_gsrb4 on a level split over GPUs, plan_deep in
-  // omg_plan.cpp): the remote boxes the columns read are proxy boxes
-  // n .. n+n_prox-1 of every variable (vstride covers them); before a pass the
+  // omg_plan.cpp, its columns in omg_columns.cpp): the remote boxes the
+  // columns read are proxy boxes n .. n+n_prox-1 of every variable (vstride covers them); before a pass the
   // cells the columns read travel as 4^3-cell bricks, phi of the colour the
   // pass reads (deep, 32 doubles per brick) and rhs when it changed since
   // (deep_rhs, 64: both colours); after it the remote faces' ghosts by the

@@ -1,9 +1,7 @@
 // omg_plan.cpp — what omg_tree_setup builds on one rank from the tree: the
-// levels' arenas and face tables, the communication plans of every exchange,
-// the column records of the block kernels and the deep halo of split levels.
+// levels' arenas and face tables, the communication plans of every exchange
+// and the deep halo of split levels (the block kernels' tables: omg_columns.cpp).
 #include <algorithm>
-#include <cmath>
-#include <numeric>
 
 #include "omg_host.h"
 
@@ -201,7 +199,7 @@ void free_levels(omg_ctx* c) {
     dfree(L.d_rhs_lex);
     dfree(L.d_xlay);
     dfree(L.d_galt);
-    dfree(L.d_phi_buf); dfree(L.d_b3); dfree(L.d_b3c); L.n_b3 = 0; L.h_b3.clear();
+    dfree(L.d_phi_buf); dfree(L.d_b3); dfree(L.d_b3c); L.n_b3 = 0; L.h_b3.clear(); L.h_b3c.clear();
     dfree(L.d_physbox);
     for (auto& P : L.dense) P.buf.release();
     L.dense.clear();
@@ -221,241 +219,6 @@ void free_levels(omg_ctx* c) {
     c->h_face_type_lvl[iv].clear();
     dfree(c->d_face_data[iv]);
   }
-}
-
-// whether k_gsrb3's 32-bit byte offsets reach every box of a variable
-static bool block3_addressable(long long n_boxes, long long stride) {
-  return (unsigned long long)n_boxes * (unsigned long long)stride * 8ull <= 0xFFFFFFFFull;
-}
-
-// boxes per column in z: 16 on levels of >= 32768 boxes, 4 down to 4096, below
-// that (levels that take the passes with OMG_BLOCK3_MIN_BOXES lowered) 2, for
-// more workgroups (OMG_BLOCK3_SMALL_COL); OMG_BLOCK3_COLUMN: all levels
-static int b3_column(const omg_ctx* c, int n) {
-  if (c->b3_col) return c->b3_col;
-  return n / (kB3TX * 8) >= 2048 ? 16 : (n >= kB3MinBoxes ? 4 : c->b3_col_small);
-}
-
-// k_gsrb3's columns (launch_gsrb3): a level of at least kB3MinBoxes boxes of
-// 16^3 whose faces are all same-GPU boxes of the level or physical (a uniform
-// level on one GPU) is tiled by columns of kB3TX boxes in x and up to kB3MaxZ
-// in z, each with the boxes around it; the level then gets phi's second
-// buffer.  Columns are ordered by z block, then Morton order in x / y, so that
-// each XCD's run of workgroups (xcd_box) is one compact patch whose halo
-// columns its own L2 holds.  A physical face (round 6) is a flag of the
-// column (kB3LenMask), the same for all its boxes, and the slot across it names
-// the box whose face it is.  Any face or tiling that does not fit: no records.
-static void build_block3(omg_ctx* c, Level& L) {
-  if (g_host_only || c->host_only || L.nc != 16 || L.n < c->b3_min_boxes || L.replicated || L.deep) return;
-  // k_gsrb3 / k_gsrb4 address a variable with 32-bit byte offsets
-  // (omg_block.hip b3_ld / b3_st): 95,325 boxes of 16^3 at most
-  if (!block3_addressable(L.n + L.n_prox, L.stride)) return;
-  for (int8_t k : L.h_nbk)
-    if (k != NB_LOCAL && !(k == NB_PHYS && !c->no_block3_phys)) return;
-  const int n = L.n;
-  // face f: 0 x-, 1 x+, 2 y-, 3 y+, 4 z-, 5 z+; across a physical face the box itself
-  auto phys = [&](int b, int f) { return L.h_nbk[(size_t)b * 6 + f] == NB_PHYS; };
-  auto nb = [&](int b, int f) { return phys(b, f) ? b : L.h_nba[(size_t)b * 6 + f]; };
-  auto ixd = [&](int b, int d) { return c->ix[(size_t)(L.ids[b] - 1) * 3 + d] - 1; };
-  auto spread = [](unsigned v) {
-    unsigned long long r = 0;
-    for (int q = 0; q < 20; q++) r |= (unsigned long long)((v >> q) & 1u) << (2 * q);
-    return r;
-  };
-  std::vector<std::pair<unsigned long long, std::vector<int>>> cols;
-  std::vector<int> covered(n, 0);
-  bool any_phys = false;
-  // columns of 16 boxes on levels of >= 32768 boxes, else 4: C3's level 1
-  // 857 / 759 us per pass against 875 / 772 with 8 (1024 workgroups, fewer
-  // halo planes per box; profiles/r05/s40_block3_z16_ab.txt) and 898 / 789
-  // with 4 (s38); on its 4096-box level 8 gained nothing, and two-box columns,
-  // twice the workgroups, took 110 us a pass against 102
-  const int nzb = b3_column(c, L.n);
-  static_assert(kB3MaxZ >= 16, "column records hold 16 boxes");
-  for (int h = 0; h < n; h++) {
-    if (ixd(h, 0) % kB3TX || ixd(h, 2) % nzb) continue;
-    std::vector<int> zc{h};
-    while ((int)zc.size() < nzb && !phys(zc.back(), 5)) {
-      const int up = nb(zc.back(), 5);
-      if (ixd(up, 2) % nzb == 0) break;   // the next column's first box
-      zc.push_back(up);
-    }
-    const int len = (int)zc.size();
-    // the column's physical faces: x-, x+, y-, y+ alike for all its boxes (and
-    // none between the tile's boxes), z- of its first box, z+ of its last
-    int fl = (phys(zc[0], 4) ? 16 : 0) | (phys(zc[len - 1], 5) ? 32 : 0);
-    for (int z = 0; z < len; z++) {
-      int t[kB3TX];
-      t[0] = zc[z];
-      for (int xs = 1; xs < kB3TX; xs++) {
-        if (phys(t[xs - 1], 1)) return;
-        t[xs] = nb(t[xs - 1], 1);
-      }
-      int f = (phys(t[0], 0) ? 1 : 0) | (phys(t[kB3TX - 1], 1) ? 2 : 0);
-      for (int xs = 0; xs < kB3TX; xs++) {
-        const int fy = (phys(t[xs], 2) ? 4 : 0) | (phys(t[xs], 3) ? 8 : 0);
-        if (xs && fy != (f & 12)) return;
-        f |= fy;
-      }
-      if (z && f != (fl & 15)) return;
-      fl |= f;
-    }
-    any_phys |= fl != 0;
-    std::vector<int> r(kB3Rec, 0);
-    r[0] = len | fl << 8;
-    for (int zs = 0; zs <= len + 1; zs++) {
-      const int cb = zs == 0 ? nb(zc[0], 4) : (zs == len + 1 ? nb(zc[len - 1], 5) : zc[zs - 1]);
-      int* row = &r[1 + kB3S * zs];
-      // the tile's row of boxes along x, then the rows below and above it in
-      // y; a grid: the rows' x neighbours agree with the y neighbours' chain
-      // (except where a slot stands across a physical face)
-      row[kB3TX + 2] = nb(cb, 0);
-      for (int xs = 1; xs <= kB3TX + 1; xs++) row[(kB3TX + 2) + xs] = xs == 1 ? cb : nb(row[(kB3TX + 2) + xs - 1], 1);
-      for (int xs = 0; xs < kB3TX + 2; xs++) {
-        const int mid = row[(kB3TX + 2) + xs];
-        row[xs] = nb(mid, 2);
-        row[2 * (kB3TX + 2) + xs] = nb(mid, 3);
-        if (zs >= 1 && zs <= len && xs >= 1 && xs <= kB3TX) covered[mid]++;
-      }
-      for (int ys = 0; ys < 3; ys += 2)
-        for (int xs = (fl & 1) ? 1 : 0; xs + 1 < kB3TX + ((fl & 2) ? 1 : 2); xs++)
-          if (nb(row[(kB3TX + 2) * ys + xs], 1) != row[(kB3TX + 2) * ys + xs + 1]) return;
-    }
-    const unsigned long long key = ((unsigned long long)(ixd(h, 2) / nzb) << 40) |
-                                   (spread((unsigned)(ixd(h, 0) / kB3TX)) | (spread((unsigned)ixd(h, 1)) << 1));
-    cols.emplace_back(key, std::move(r));
-  }
-  for (int b = 0; b < n; b++)
-    if (covered[b] != 1) return;
-  std::sort(cols.begin(), cols.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-  std::vector<int> flat;
-  flat.reserve(cols.size() * kB3Rec);
-  for (auto& cr : cols) flat.insert(flat.end(), cr.second.begin(), cr.second.end());
-  L.n_b3 = (int)cols.size();
-  L.b3_phys = any_phys;
-  L.d_b3 = to_device(flat);
-  L.h_b3 = std::move(flat);
-  dmalloc(&L.d_phi_buf, sizeof(double) * (size_t)L.n * L.stride, true);
-}
-
-// The ghost terms of the block passes' physical faces: bc_to_gc's c0 * b, c1,
-// c2 per face (m_ghost_cells.f90:665-766; k_gsrb_tile's phys_ghost, the same
-// expressions), for constant boundary values only; false when the level's
-// are tabulated (a boundary callback) or stored with phi.
-static bool b3_phys_args(omg_ctx* c, int lvl, const Level& L, B3Phys& P) {
-  if (c->phi_bc_data_stored) return false;
-  auto it = c->d_face_off_lvl[0].find(lvl);
-  if (it != c->d_face_off_lvl[0].end() && it->second) return false;
-  for (int nb = 1; nb <= 6; nb++) {
-    const int type = c->bc[0].type[nb - 1];
-    const double bv = c->bc[0].value[nb - 1];
-    double c0, c1, c2;
-    if (type == OMG_BC_DIRICHLET) {
-      c0 = 2; c1 = -1; c2 = 0;
-    } else if (type == OMG_BC_NEUMANN) {
-      c0 = L.dr[(nb - 1) >> 1] * ((nb & 1) ? -1.0 : 1.0); c1 = 1; c2 = 0;
-    } else {
-      c0 = 0; c1 = 2; c2 = -1;
-    }
-    P.k[nb - 1] = c0 * bv;
-    P.c1[nb - 1] = c1;
-    P.c2[nb - 1] = c2;
-  }
-  return true;
-}
-
-// whether a block pass (k_gsrb3 / k_gsrb4) may smooth the level now: records,
-// consistent ghosts, an operator it has; ph: its physical faces' terms (null:
-// none), P their storage
-bool b3_usable(omg_ctx* c, int lvl, B3Phys& P, const B3Phys*& ph) {
-  const Level* L = level_ptr(c, lvl);
-  ph = nullptr;
-  if (!L || !L->d_b3 || !(L->phi_gc_ok || (L->gc_deferred && !L->b3_phys)) || !gsrb3_op_ok(c->op) ||
-      c->no_block3)
-    return false;
-  if (L->b3_phys) {
-    if (!b3_phys_args(c, lvl, *L, P)) return false;
-    ph = &P;
-  }
-  return true;
-}
-
-// k_gsrb3's correct_children form (launch_gsrb3's ccols) for the columns of F:
-// every column of an even number of boxes starts at a coarse box's corner in x
-// and z, its fine boxes are the children of its coarse boxes, and every coarse
-// box is the own box of exactly two columns (its two halves in y), on a
-// coarse level of 16^3 boxes whose faces are all same-GPU boxes.
-static void build_block3c(omg_ctx* c, Level& F, const Level& C) {
-  if (F.h_b3.empty() || C.nc != 16 || C.replicated || C.n == 0 || F.n != 8 * C.n || F.deep != C.deep) return;
-  if (!block3_addressable(C.n + C.n_prox, C.stride)) return;
-  if (!F.deep)
-    for (int8_t k : C.h_nbk)
-      if (k != NB_LOCAL) return;
-  for (int b = 0; b < F.n; b++)
-    if (F.parent_local[b] < 0) return;
-  // the coarse boxes by their neighbours: C's own table on one GPU; on a
-  // split level (deep halo on both levels) the global tree, a box on another
-  // rank standing for its proxy in C's arena (deep_res fills its res)
-  Tree T{c};
-  auto cslot = [&](int id) {
-    if (id > 0 && T.rank(id) == c->rank) return c->local_index[id];
-    auto it = std::lower_bound(C.prox_ids.begin(), C.prox_ids.end(), id);
-    return it != C.prox_ids.end() && *it == id ? C.n + (int)(it - C.prox_ids.begin()) : -1;
-  };
-  auto cid = [&](int x) { return x < C.n ? C.ids[x] : C.prox_ids[x - C.n]; };
-  auto nbc = [&](int b, int f) {
-    if (!F.deep) return C.h_nba[(size_t)b * 6 + f];
-    const int id = T.nbr(cid(b), f + 1);
-    return id > 0 ? cslot(id) : -1;
-  };
-  auto dix = [&](int b, int q) { return (F.dix_packed[b] >> (10 * q)) & 1023; };
-  std::vector<int> out((size_t)F.n_b3 * kB3CRec, 0);
-  std::vector<int> own(C.n, 0);
-  for (int q = 0; q < F.n_b3; q++) {
-    const int* r = &F.h_b3[(size_t)q * kB3Rec];
-    if (r[0] > kB3LenMask) return;   // (physical faces: the plain passes only)
-    const int len = r[0], lenc = len / 2;
-    if (len % 2) return;
-    auto fine = [&](int zs, int xs) { return r[1 + kB3S * zs + (kB3TX + 2) + xs]; };
-    const int b0 = fine(1, 1);
-    if (dix(b0, 0) != 0 || dix(b0, 2) != 0) return;
-    int* o = &out[(size_t)q * kB3CRec];
-    o[0] = dix(b0, 1);
-    int zc[kB3MaxZ / 2 + 2];
-    zc[1] = F.parent_local[b0];
-    for (int z = 2; z <= lenc; z++) zc[z] = nbc(zc[z - 1], 5);
-    if (F.deep)
-      for (int z = 2; z <= lenc; z++)
-        if (zc[z] < 0 || zc[z] >= C.n) return;   // (a column's coarse boxes are this rank's)
-    zc[0] = nbc(zc[1], 4);
-    zc[lenc + 1] = nbc(zc[lenc], 5);
-    for (int z = 0; z <= lenc + 1; z++) {
-      int* row = o + 1 + 9 * z;
-      row[4] = zc[z];
-      row[3] = nbc(zc[z], 0);
-      row[5] = nbc(zc[z], 1);
-      for (int xs = 0; xs < 3; xs++) {
-        row[xs] = nbc(row[3 + xs], 2);
-        row[6 + xs] = nbc(row[3 + xs], 3);
-      }
-      for (int q2 = 0; q2 < 9; q2++)
-        if (row[q2] < 0) return;
-      for (int ys = 0; ys < 3; ys += 2)
-        for (int xs = 0; xs < 2; xs++)
-          if (nbc(row[3 * ys + xs], 1) != row[3 * ys + xs + 1]) return;
-      if (z >= 1 && z <= lenc) own[zc[z]]++;
-    }
-    for (int zs = 1; zs <= len; zs++)
-      for (int xs = 1; xs <= kB3TX; xs++) {
-        const int fb = fine(zs, xs);
-        if (F.parent_local[fb] != zc[(zs + 1) / 2] || dix(fb, 0) != (xs - 1) * 8 || dix(fb, 1) != o[0] ||
-            dix(fb, 2) != ((zs - 1) & 1) * 8)
-          return;
-      }
-  }
-  for (int b = 0; b < C.n; b++)
-    if (own[b] != 2) return;
-  F.d_b3c = to_device(out);
 }
 
 // ---------------------------------------------------------------------------
@@ -485,7 +248,7 @@ static void build_block3c(omg_ctx* c, Level& F, const Level& C) {
 // follow; a level with parents gets its rhs from update_coarse every cycle,
 // so its proxies' rhs travels once per cycle.  Such a level (C3's level 0 at
 // N > 1) also stores res for the correction form above it (the RES pass), and
-// its proxies get that res too (deep_res).
+// its proxies get that res too (deep_res).  (The columns: omg_columns.cpp.)
 // the box at offset o (components -1..1) from id, walking x, y, z in turn
 // (zyx: the reverse order); 0 when the walk leaves the level's boxes
 static int deep_walk(const Tree& T, int id, const int o[3], bool zyx = false) {
@@ -586,16 +349,13 @@ static void plan_deep(omg_ctx* c, Level& L) {
       give[{q, id}] |= deep_bricks(o);
     });
   }
-  std::map<int, int> pidx;
-  for (auto& kv : need) {
-    pidx[kv.first] = L.n + (int)L.prox_ids.size();
+  std::vector<Rec> rs, rr;
+  for (auto& kv : need) {   // (ascending ids: a proxy's slot is n + its place in prox_ids)
+    for (int br = 0; br < 64; br++)
+      if ((kv.second >> br) & 1) rr.push_back({T.rank(kv.first), 64LL * kv.first + br, L.n + (int)L.prox_ids.size(), br});
     L.prox_ids.push_back(kv.first);
   }
   L.n_prox = (int)L.prox_ids.size();
-  std::vector<Rec> rs, rr;
-  for (auto& kv : need)
-    for (int br = 0; br < 64; br++)
-      if ((kv.second >> br) & 1) rr.push_back({T.rank(kv.first), 64LL * kv.first + br, pidx[kv.first], br});
   for (auto& kv : give)
     for (int br = 0; br < 64; br++)
       if ((kv.second >> br) & 1)
@@ -608,65 +368,6 @@ static void plan_deep(omg_ctx* c, Level& L) {
     finalize_transfer(*X);
   }
   L.prox_rhs_ok = false;
-  // the columns (build_block3's, over global ids: a column's boxes are this
-  // rank's, the boxes around it this rank's or proxies)
-  auto mine = [&](int id) { return id > 0 && T.rank(id) == me; };
-  auto slot = [&](int id) {
-    if (mine(id)) return c->local_index[id];
-    auto it = pidx.find(id);
-    if (it == pidx.end()) throw OmgError("plan_deep: a column reads a box outside the proxies");
-    return it->second;
-  };
-  const int nzb = b3_column(c, L.n);
-  std::vector<std::pair<unsigned long long, std::vector<int>>> cols;
-  std::vector<int> covered(L.n, 0);
-  auto spread = [](unsigned v) {
-    unsigned long long r = 0;
-    for (int q = 0; q < 20; q++) r |= (unsigned long long)((v >> q) & 1u) << (2 * q);
-    return r;
-  };
-  for (int h : L.ids) {
-    if (!mine(h) || ixd(h, 0) % kB3TX || !(ixd(h, 2) % nzb == 0 || !mine(T.nbr(h, 5)))) continue;
-    std::vector<int> zc{h};
-    while ((int)zc.size() < nzb) {
-      const int up = T.nbr(zc.back(), 6);
-      if (!mine(up) || ixd(up, 2) % nzb == 0) break;
-      zc.push_back(up);
-    }
-    const int len = (int)zc.size();
-    std::vector<int> r(kB3Rec, 0);
-    r[0] = len;
-    for (int zs = 0; zs <= len + 1; zs++) {
-      const int cb = zs == 0 ? T.nbr(zc[0], 5) : (zs == len + 1 ? T.nbr(zc[len - 1], 6) : zc[zs - 1]);
-      int g[3][kB3TX + 2];
-      g[1][0] = T.nbr(cb, 1);
-      for (int xs = 1; xs <= kB3TX + 1; xs++) g[1][xs] = xs == 1 ? cb : T.nbr(g[1][xs - 1], 2);
-      for (int xs = 0; xs < kB3TX + 2; xs++) {
-        g[0][xs] = T.nbr(g[1][xs], 3);
-        g[2][xs] = T.nbr(g[1][xs], 4);
-      }
-      for (int ys = 0; ys < 3; ys++)
-        for (int xs = 0; xs < kB3TX + 2; xs++) {
-          if (zs >= 1 && zs <= len && ys == 1 && xs >= 1 && xs <= kB3TX) {
-            if (!mine(g[ys][xs])) throw OmgError("plan_deep: a column box on another rank");
-            covered[c->local_index[g[ys][xs]]]++;
-          }
-          r[1 + kB3S * zs + (kB3TX + 2) * ys + xs] = slot(g[ys][xs]);
-        }
-    }
-    const unsigned long long key = ((unsigned long long)(ixd(h, 2) / nzb) << 40) |
-                                   (spread((unsigned)(ixd(h, 0) / kB3TX)) | (spread((unsigned)ixd(h, 1)) << 1));
-    cols.emplace_back(key, std::move(r));
-  }
-  for (int b = 0; b < L.n; b++)
-    if (covered[b] != 1) throw OmgError("plan_deep: the columns do not cover the level once");
-  std::sort(cols.begin(), cols.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-  std::vector<int> flat;
-  flat.reserve(cols.size() * kB3Rec);
-  for (auto& cr : cols) flat.insert(flat.end(), cr.second.begin(), cr.second.end());
-  L.n_b3 = (int)cols.size();
-  L.d_b3 = to_device(flat);
-  L.h_b3 = std::move(flat);
 }
 
 namespace {
@@ -684,7 +385,6 @@ struct Planner {
   void parents_leaves(int l, Level& L);
   void grid_transfers();
   void buffers();
-  void agree_block3c();
 };
 
 // which levels are replicated, the boxes of every level that live here
@@ -995,7 +695,7 @@ void Planner::grid_transfers() {
         }
       }
     }
-    build_block3c(c, F, C);
+    build_coarse_columns(c, F, C);
   }
 }
 
@@ -1031,21 +731,6 @@ void Planner::buffers() {
   }
 }
 
-void Planner::agree_block3c() {
-  // k_gsrb3 / k_gsrb4's correction form on split levels: which path the
-  // up-smoothing takes decides collective rounds (the deep halo of both
-  // levels, deep_res), and whether the coarse records could be built depends
-  // on each rank's boxes, so the ranks agree: every rank holding boxes of the
-  // level must have them, else none uses them
-  if (c->n_ranks > 1 && !c->host_only)
-    for (int l = c->lowest + 1; l <= c->highest; l++) {
-      Level& F = c->levels[l];
-      if (!F.deep) continue;
-      const bool fail = F.n > 0 && !F.d_b3c;
-      if (allreduce(c, fail ? 1.0 : 0.0, true) > 0.5) dfree(F.d_b3c);
-    }
-}
-
 }  // namespace
 
 void build_plan(omg_ctx* c) {
@@ -1061,7 +746,6 @@ void build_plan(omg_ctx* c) {
       const size_t bytes = sizeof(double) * (size_t)c->n_vars * (L.n + L.n_prox) * L.stride;
       dmalloc(&L.d_data, bytes, true);
       L.d_phi = L.d_data;
-      if (L.deep && L.n_b3) dmalloc(&L.d_phi_buf, sizeof(double) * (size_t)(L.n + L.n_prox) * L.stride, true);
       if (c->debug && !g_host_only) {   // (L.view() needs only the arena fields here)
         launch_poison_ghosts(L.view(), c->n_vars, snan_value(), nullptr);
         HIPCHK(hipDeviceSynchronize());
@@ -1070,7 +754,7 @@ void build_plan(omg_ctx* c) {
     const std::vector<int> sendpos = P.faces(l, L);
     P.boundary_lists(L);
     L.d_phi = L.d_data;
-    build_block3(c, L);
+    build_columns(c, L);
     L.d_sendpos = to_device(sendpos);
     L.d_nbk = to_device(L.h_nbk);
     L.d_nba = to_device(L.h_nba);
@@ -1081,7 +765,7 @@ void build_plan(omg_ctx* c) {
   }
   P.grid_transfers();
   P.buffers();
-  P.agree_block3c();
+  agree_columns(c);
   ensure_rhs_lex(c);
   rbh_build(c);
 }

@@ -28,6 +28,7 @@ SIGNATURES = {
     "omg_device_count": (_I, [C.POINTER(_I)]),
     "omg_plan_transfer": (_I, [_P, _I, _I, _I, _I, _IP, C.POINTER(C.c_longlong), C.POINTER(_I),
                                C.POINTER(_I)]),
+    "omg_plan_columns": (_I, [_P, _I, _I, _I, _IP, C.POINTER(_I), C.POINTER(_I)]),
     "omg_ctx_create": (_I, [C.POINTER(_P), _I, _I, _I, C.c_char_p]),
     "omg_ctx_destroy": (_I, [_P]),
     "omg_tree_setup": (_I, [_P, _I, _IP, _IP, _IP, _IP, _IP, _IP, _I, _I, _I, _I, _IP, _DP,
@@ -227,6 +228,16 @@ class Context:
         self.call("plan_transfer", lvl, which, direction, n.value, peers,
                   keys.ctypes.data_as(C.POINTER(C.c_longlong)), C.byref(n), C.byref(per))
         return [(int(p), int(k)) for p, k in zip(peers[:n.value], keys[:n.value])], per.value
+
+    def plan_columns(self, lvl, which):
+        """The block passes' tables of a level as an (n_cols, rec_ints) int32
+        array: which 0 the column records, 1 the coarse records
+        (omg_plan_columns); n_cols is 0 where the level has none."""
+        n, per = _I(), _I()
+        self.call("plan_columns", lvl, which, 0, np.zeros(1, np.int32), C.byref(n), C.byref(per))
+        recs = np.zeros(max(n.value * per.value, 1), np.int32)
+        self.call("plan_columns", lvl, which, recs.size, recs, C.byref(n), C.byref(per))
+        return recs[:n.value * per.value].reshape(n.value, per.value)
 
     def stream(self) -> int:
         return self.L.omg_stream(self.h) or 0

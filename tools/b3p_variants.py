@@ -4,7 +4,7 @@ octree-mg_amd/_variants/libomg_b3p_<name>.so (load with OMG_LIB=...)."""
 import os, shutil, subprocess, sys
 
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILES = {"subnt": "omg_tiles.hip", "subntld": "omg_tiles.hip", "z8": "omg_plan.cpp", "z2": "omg_plan.cpp"}
+FILES = {"subnt": "omg_tiles.hip", "subntld": "omg_tiles.hip"}
 # (default: omg_block.hip)
 VARIANTS = {
     # the plain pass at 6 waves per SIMD (3 workgroups per CU; 79 VGPRs, 20 B
