@@ -389,6 +389,67 @@ int omg_get_boxes_grad(omg_ctx *ctx, int iv, int n_boxes, const int *ids,
                        const long long stride[3], double scale, int centering,
                        int fill, void *stream, long long *n_cells);
 
+/* The divergence of a vector field in block layout, in DEVICE memory, into
+ * variable iv: the first step of a projection (rhs = div B; solve; B -= grad
+ * phi), computed from the host's component pools in one pass with no scratch
+ * pool in between: the mirror image of omg_get_boxes_grad.  ids, box_off,
+ * stride, stream, the plan-only behaviour and the ownership, range and
+ * "listed twice" checks are exactly omg_get_boxes_grad's.  dev[d] is the pool
+ * of component d (0 x, 1 y, 2 z) of the field V; a NULL dev[d] skips that
+ * component.  The pools are only read, so they may interleave, overlap or be
+ * one and the same pointer.
+ * With o(i,j,k) = box_off[q] + (i-1) + (j-1)*stride[1] + (k-1)*stride[2], for
+ * every interior cell 1 <= i,j,k <= nc of every listed box variable iv is
+ * overwritten with the sum of the terms t_d of the non-NULL components in the
+ * order x, y, z: (t_x + t_y) + t_z, two components t_a + t_b, one alone t_d.
+ * centering == 0, cell-centred: V_d(i,j,k) at dev[d][o(i,j,k)],
+ *     t_d = (V_d(+1 in d) - V_d(-1 in d)) * f_d,   f_d = (0.5 * scale) / dr_d;
+ * read are the block's interior and its six face-ghost layers (index 0 and
+ * nc+1 along d, the two others in 1..nc); stride[1] >= m and
+ * stride[2] >= stride[1]*m with m = nc_max + 2.
+ * centering == 1, face-centred: dev[d][o(i,j,k)] is V_d on the face between
+ * the cells i and i+1 along d, the layout omg_get_boxes_grad writes with
+ * centering 1,
+ *     t_d = (V_d(i,j,k) - V_d(-1 in d)) * f_d,     f_d = scale / dr_d;
+ * read is the index along d from 0 to nc, the two others in 1..nc;
+ * m = nc_max + 1 in the stride rule.  The face-centred divergence of the
+ * face-centred gradient is the 7-point Laplacian the solver inverts.
+ * f_d is computed on the host in double with the dr of each box's level (a
+ * list mixes levels): one subtraction and one multiplication per term, then
+ * the additions as written, no contraction, signed zeros as IEEE gives them.
+ * Pool elements outside those named are never read: edges, corners, outer
+ * ghost layers, a NULL component's pool.  The face-ghost slots of iv, every
+ * other variable and boxes not listed keep their bits.
+ * *n_cells (if non-NULL) = the cells written, sum of nc^3, counted on the
+ * host.
+ * State: exactly omg_put_boxes's with ghost == 0 (a writer: pending work is
+ * applied first, derived copies of rhs are dropped; iv == 1 makes the phi
+ * ghosts of every level stale and is collective in the same sense; a box on
+ * a replicated level is refused).
+ * Errors (nothing is launched, no state is touched): omg_get_boxes_grad's
+ * list errors; a centering other than 0 or 1; all three pointers NULL with
+ * n_boxes > 0; a non-NULL pool that is not device memory of the context's
+ * GPU, or whose touched range leaves its allocation: from box_off - stride[d]
+ * of the lowest block to the last interior element of the highest, plus
+ * stride[d] for cell centring (stride[0] = 1).
+ * The call shares the context's cache of four lists with the other block
+ * entries (the same records; its centring is part of the key and distinct
+ * from the copies' and the gradient's): a cached list uploads nothing and
+ * never waits on the host.
+ * Kernels: a per-cell kernel for every box size, which measured faster or
+ * equal at every list length, and a tile kernel for 16^3 and 8^3 boxes that
+ * reads the pools from global memory (16-B loads when every base, box_off
+ * and stride is even, 8-B loads otherwise) and writes the stored box as
+ * same-colour pairs with 16-B stores, kept for A/B timing and the tests'
+ * cross-check under OMG_BOXES_TILE=1; both give the same bits.
+ * OMG_BOXES_GENERIC=1 and OMG_BOXES_TILE=1 apply as they do to omg_put_boxes.
+ * Profiling families: boxes_div (the call), boxes_div_tile (the tile kernel,
+ * per level). */
+int omg_put_boxes_div(omg_ctx *ctx, int iv, int n_boxes, const int *ids,
+                      const double *const dev[3], const long long *box_off,
+                      const long long stride[3], double scale, int centering,
+                      void *stream, long long *n_cells);
+
 /* The hot path.  omg_fas_vcycle = mg_fas_vcycle (src/m_multigrid.f90:150-243);
  * highest_lvl < lowest_lvl means "not present".  omg_fas_fmg = mg_fas_fmg
  * (:84-147).  max_res is written when want_max_res (the optional argument). */

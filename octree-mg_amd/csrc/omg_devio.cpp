@@ -1,8 +1,9 @@
 // omg_devio.cpp — device I/O: omg_put_dense / omg_get_dense (windows of a
 // level's cell grid, kernels in omg_dense.hip), omg_get_dense_grad (the same
 // windows of a gradient, omg_dense_grad.hip), omg_put_boxes / omg_get_boxes
-// (block lists, omg_boxes.hip) and omg_get_boxes_grad (the same lists of a
-// gradient, omg_boxes_grad.hip): the caller's device memory, in the order of
+// (block lists, omg_boxes.hip), omg_get_boxes_grad (the same lists of a
+// gradient, omg_boxes_grad.hip) and omg_put_boxes_div (the same lists from a
+// divergence, omg_boxes_div.hip): the caller's device memory, in the order of
 // the caller's stream, by cached records.  What the entries share stands first.
 #include <algorithm>
 
@@ -365,7 +366,8 @@ static void boxes_check_list(int n_boxes, const int* ids, const long long* box_o
 }
 
 // The cached records of a list, or null (a cached list was checked when it
-// was built).  centering: kBoxCopy for the copies, else omg_get_boxes_grad's.
+// was built).  centering: kBoxCopy for the copies, omg_get_boxes_grad's, or
+// kBoxDiv + omg_put_boxes_div's.
 static BoxPlan* boxes_cached(omg_ctx* c, int n_boxes, const int* ids, const long long* box_off,
                              const long long* stride, int ghost, int centering, bool aligned) {
   BoxPlan* P = nullptr;
@@ -552,6 +554,99 @@ void boxes_grad(omg_ctx* c, int iv, int n_boxes, const int* ids, double* const* 
                                c->stream);
       } else {
         launch_boxes_grad_cell(V, iv, S.buf.d + G.first, G.n, A, stride[1], stride[2], centering != 0, c->stream);
+      }
+    }
+    HIPCHK(hipGetLastError());
+  }
+  join_out(c, stream);
+}
+
+// What tools/box_div_bench.py measured for this entry's kernels (DESIGN §20,
+// 16^3 boxes, 128 .. 8000 listed boxes of one level, both centrings, pools
+// with one and two ghost layers): the per-cell kernel won at every length up
+// to 2048 boxes (2.2x at 128, 1.1x at 1536); from 4096 on both run at the
+// memory's rate, the per-cell kernel 5 % ahead with two ghost layers, within
+// 4 % either way between runs with one.  By §14's rule the tile kernel stays
+// nowhere: it is routed around and runs under OMG_BOXES_TILE=1 only.
+constexpr int kBoxesDivTileMinCell = INT_MAX;
+constexpr int kBoxesDivTileMinFace = INT_MAX;
+
+// omg_put_boxes_div: omg_put_boxes's state with ghost == 0 and
+// omg_get_boxes_grad's list, records, cache and stream ordering; up to three
+// read-only component pools that share box_off and the strides.
+void boxes_div(omg_ctx* c, int iv, int n_boxes, const int* ids, const double* const* dev, const long long* box_off,
+               const long long* stride, double scale, int centering, void* stream, long long* n_cells) {
+  const Fail fail{"omg_put_boxes_div"};
+  if (iv < 1 || iv > c->n_vars) fail("bad variable index");
+  if (centering != 0 && centering != 1) fail("centering must be 0 (cells) or 1 (faces)");
+  boxes_check_list(n_boxes, ids, box_off, stride, fail);
+  if (!dev) fail("the array of component pointers is required");
+  bool aligned = true, any = false;
+  for (int d = 0; d < 3; d++)
+    if (dev[d]) {
+      any = true;
+      aligned = aligned && ((uintptr_t)dev[d] & 15) == 0;
+    }
+  if (n_boxes > 0 && !any) fail("NULL pointers for all three components with n_boxes > 0");
+  if (c->levels.empty()) fail("no tree (omg_tree_setup)");
+  const bool generic = env_flag("OMG_BOXES_GENERIC"), force_tile = env_flag("OMG_BOXES_TILE");
+  BoxPlan* P = boxes_cached(c, n_boxes, ids, box_off, stride, 0, kBoxDiv + centering, aligned);
+  BoxPlan fresh;
+  if (P) {
+    for (int q = 0; q < n_boxes && P->any_replicated; q++)   // (refused again: a put)
+      if (level_ptr(c, c->lvl[ids[q] - 1])->replicated) refuse_replicated_put(c->lvl[ids[q] - 1], fail);
+  } else {
+    fresh.centering = kBoxDiv + centering;
+    std::copy(stride, stride + 3, fresh.stride);
+    fresh.aligned = aligned;
+    boxes_build(c, fresh, n_boxes, ids, box_off, true, fail);
+  }
+  const BoxPlan& R = P ? *P : fresh;
+  if (n_boxes > 0) {
+    // (the layer 0 along each direction, and the layer nc+1 of cell centring)
+    const long long m = R.nc_max + (centering ? 1 : 2);
+    if (stride[1] < m) fail(centering ? "stride[1] < nc + 1" : "stride[1] < nc + 2");
+    if (stride[2] / m < stride[1]) fail(centering ? "stride[2] < stride[1]*(nc + 1)" : "stride[2] < stride[1]*(nc + 2)");
+  }
+  if (c->host_only) {
+    if (n_cells) *n_cells = R.n_cells;
+    return;
+  }
+  if (n_boxes > 0) {
+    // (component d reaches one element, row or plane below its boxes'
+    // interiors, and with cell centring as far above them)
+    for (int d = 0; d < 3; d++)
+      if (dev[d])
+        check_device_range(c, dev[d], R.lo_ext - stride[d], R.hi_ext + (centering ? 0 : stride[d]), "a block", fail);
+    for (const BoxGroup& G : R.groups)
+      if ((long long)G.n * 16 > INT_MAX) fail("too many boxes for one launch");
+  }
+  // --- nothing of the state was touched up to here
+  enter(c);
+  // (every level, as box_io's put)
+  if (iv == 1) phi_dirty_all(c);
+  if (n_cells) *n_cells = R.n_cells;
+  if (n_boxes == 0) return;
+  BoxPlan& S = boxes_claim(c, P, fresh);
+  join_in(c, stream);
+  {
+    Prof p(c, "boxes_div", (double)S.n_cells);
+    for (const BoxGroup& G : S.groups) {
+      const Level* L = level_ptr(c, G.lvl);
+      const LevelView V = L->view();
+      BoxDiv A;
+      for (int d = 0; d < 3; d++) {
+        A.in[d] = dev[d];
+        A.f[d] = (centering ? scale : 0.5 * scale) / L->dr[d];
+      }
+      const bool measured = G.n >= (centering ? kBoxesDivTileMinFace : kBoxesDivTileMinCell);
+      const bool tile = !generic && boxes_tile_nc(L->nc) && (force_tile || measured);
+      if (tile) {
+        Prof pr(c, "boxes_div_tile", (double)G.n * L->nc * L->nc * L->nc, G.lvl);
+        launch_boxes_div_tile(V, iv, S.buf.d + G.first, G.n, A, stride[1], stride[2], centering != 0, G.odd,
+                              c->stream);
+      } else {
+        launch_boxes_div_cell(V, iv, S.buf.d + G.first, G.n, A, stride[1], stride[2], centering != 0, c->stream);
       }
     }
     HIPCHK(hipGetLastError());

@@ -146,6 +146,14 @@ struct DenseGrad {
   double f[3];
 };
 
+// omg_put_boxes_div's kernel argument: the component pools (null: the
+// component is skipped) and f_d = 0.5 * scale / dr_d (cells) or scale / dr_d
+// (faces).
+struct BoxDiv {
+  const double* in[3];
+  double f[3];
+};
+
 // The records of a cached plan (omg_devio.cpp): upload() grows both sides when
 // they are too small and copies the records in the order of the context
 // stream; release() is called by free_levels (no destructor calls HIP).
@@ -191,6 +199,7 @@ struct BoxGroup {
   bool odd = false;    // some row of some block is not 16-B aligned
 };
 constexpr int kBoxCopy = -1;        // BoxPlan::centering of omg_put_boxes / omg_get_boxes
+constexpr int kBoxDiv = 2;          // BoxPlan::centering of omg_put_boxes_div: kBoxDiv + its centring
 struct BoxPlan {
   // the key: the list by value, the strides, ghost, the centring and whether
   // the base (omg_get_boxes_grad: every non-null base) is 16-B aligned
@@ -198,7 +207,7 @@ struct BoxPlan {
   std::vector<long long> off;
   long long stride[3] = {0, 0, 0};
   int ghost = 0;
-  int centering = kBoxCopy;         // omg_get_boxes_grad: 0 cell-, 1 face-centred values
+  int centering = kBoxCopy;         // omg_get_boxes_grad: 0 cell-, 1 face-centred values; omg_put_boxes_div: 2, 3
   bool aligned = false;
   std::vector<BoxRec> recs;         // (grouped; uploaded through buf)
   std::vector<BoxGroup> groups;

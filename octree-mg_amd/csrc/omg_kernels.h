@@ -228,6 +228,17 @@ void launch_boxes_grad_tile(const LevelView& L, int iv, const BoxRec* recs, int 
                             long long s2, bool face, bool w8, hipStream_t st);
 void launch_boxes_grad_cell(const LevelView& L, int iv, const BoxRec* recs, int n, const DenseGrad& G, long long s1,
                             long long s2, bool face, hipStream_t st);
+// omg_put_boxes_div (omg_boxes_div.hip): the divergence of the vector field in
+// the component pools G.in[d] (null: skipped; blocks laid out as above) into
+// variable iv's interior cells of the boxes of one level listed by records.
+// face = false: (V_d(+1 in d) - V_d(-1 in d)) * G.f[d]; face = true:
+// (V_d - V_d(-1 in d)) * G.f[d]; summed over d in the order x, y, z.  The tile
+// kernel takes boxes of boxes_tile_nc() sizes (w8: 8-B loads, for blocks that
+// are not 16-B aligned), the per-cell kernel any box.
+void launch_boxes_div_tile(const LevelView& L, int iv, const BoxRec* recs, int n, const BoxDiv& G, long long s1,
+                           long long s2, bool face, bool w8, hipStream_t st);
+void launch_boxes_div_cell(const LevelView& L, int iv, const BoxRec* recs, int n, const BoxDiv& G, long long s1,
+                           long long s2, bool face, hipStream_t st);
 void launch_phi_bc_store(const LevelView& L, const GcBC& bc, int* nba, hipStream_t st);
 
 // The coarse end of the V-cycle in ONE single-workgroup launch (omg_tiles.hip):

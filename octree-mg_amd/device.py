@@ -52,6 +52,8 @@ SIGNATURES = {
                            C.POINTER(_LL)]),
     "omg_get_boxes_grad": (_I, [_P, _I, _I, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, _LP, _D, _I, _I,
                                 C.c_void_p, C.POINTER(_LL)]),
+    "omg_put_boxes_div": (_I, [_P, _I, _I, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, _LP, _D, _I, C.c_void_p,
+                               C.POINTER(_LL)]),
     "omg_fas_vcycle": (_I, [_P, _I, _I, C.POINTER(_D), _I]),
     "omg_fas_fmg": (_I, [_P, _I, _I, C.POINTER(_D)]),
     "omg_apply_op": (_I, [_P, _I]),
@@ -340,6 +342,28 @@ class Context:
                   None if off is None else off.ctypes.data_as(C.c_void_p),
                   np.ascontiguousarray(stride, dtype=np.int64).reshape(3), float(scale), int(centering),
                   int(bool(fill)), C.c_void_p(int(stream) or None), C.byref(cells))
+        return cells.value
+
+    def put_boxes_div(self, iv, ids, ptrs, box_off, stride, scale=1.0, centering=0, stream=0):
+        """omg_put_boxes_div: variable iv of the boxes `ids` becomes the
+        divergence of the vector field whose component pools lie at the device
+        addresses ptrs = (x, y, z) (0 / None: that component is skipped), which
+        share box_off and stride as omg_put_boxes lays blocks out.
+        centering 0: the sum of (V_d(+1 in d) - V_d(-1 in d)) * 0.5 * scale /
+        dr_d, V_d at the cells; 1: of (V_d - V_d(-1 in d)) * scale / dr_d, V_d
+        at the faces 0 .. nc along d, face i at cell i's slot.  Returns the
+        cells written."""
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        off = None if box_off is None else np.ascontiguousarray(box_off, dtype=np.int64).reshape(-1)
+        n = 0 if ids is None else ids.size
+        if off is not None and ids is not None and off.size != n:
+            raise ValueError(f"put_boxes_div: {n} ids and {off.size} offsets")
+        dev = (C.c_void_p * 3)(*[C.c_void_p(int(p or 0) or None) for p in ptrs])
+        cells = _LL(0)
+        self.call("put_boxes_div", iv, n, None if ids is None else ids.ctypes.data_as(C.c_void_p), dev,
+                  None if off is None else off.ctypes.data_as(C.c_void_p),
+                  np.ascontiguousarray(stride, dtype=np.int64).reshape(3), float(scale), int(centering),
+                  C.c_void_p(int(stream) or None), C.byref(cells))
         return cells.value
 
     def scalar(self, name, *args):

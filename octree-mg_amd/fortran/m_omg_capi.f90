@@ -19,6 +19,7 @@ module m_omg_capi
   public :: omg_level_size, omg_upload_level, omg_download_level
   public :: omg_put_dense, omg_get_dense, omg_get_dense_grad
   public :: omg_put_boxes, omg_get_boxes, omg_get_boxes_grad
+  public :: omg_put_boxes_div
   public :: omg_fas_vcycle, omg_fas_fmg, omg_apply_op, omg_phi_bc_store
   public :: omg_synchronize, omg_diffusion_solve
   public :: omg_poisson_free_3d, omg_free_planes
@@ -254,6 +255,24 @@ module m_omg_capi
        type(c_ptr), value               :: stream, n_cells
        integer(c_int) :: ierr
      end function omg_get_boxes_grad
+
+     ! omg_put_boxes_div (include/omg.h): dev holds the three component
+     ! pools' device pointers (x, y, z; c_null_ptr skips a component), which
+     ! share box_off and stride and are only read; scale and centering go by
+     ! value
+     function omg_put_boxes_div(ctx, iv, n_boxes, ids, dev, box_off, stride, scale, centering, &
+          stream, n_cells) bind(C, name="omg_put_boxes_div") result(ierr)
+       import :: c_ptr, c_int, c_long_long, c_double
+       type(c_ptr), value               :: ctx
+       integer(c_int), value            :: iv, n_boxes
+       integer(c_int), intent(in)       :: ids(*)
+       type(c_ptr), intent(in)          :: dev(3)
+       integer(c_long_long), intent(in) :: box_off(*), stride(3)
+       real(c_double), value            :: scale
+       integer(c_int), value            :: centering
+       type(c_ptr), value               :: stream, n_cells
+       integer(c_int) :: ierr
+     end function omg_put_boxes_div
 
      function omg_fas_vcycle(ctx, highest_lvl, want_max_res, max_res, standalone) &
           bind(C, name="omg_fas_vcycle") result(ierr)

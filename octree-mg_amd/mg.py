@@ -368,6 +368,58 @@ class MG(MGTree):
                                         torch.cuda.current_stream(used[0].device).cuda_stream)
         return out, cells
 
+    def set_blocks_div(self, iv, blocks, ids, ghost_width, scale=1.0, centering="cell",
+                       components=(True, True, True)):
+        """omg_put_boxes_div: variable iv of the boxes `ids` (as set_blocks lists
+        them) becomes the divergence of the vector field in `blocks`, a
+        torch.float64 tensor [3, n, m, m, m] on the context's GPU (x, y, z
+        components, m = nc + 2 * ghost_width), or a sequence of three tensors
+        [n, m, m, m] or Nones of one shape and one set of strides; the layout
+        checks are get_blocks_grad's, and since nothing is written the
+        components may be one and the same tensor.  A component that is None
+        or whose entry of `components` is false is skipped and never read.
+        ghost_width >= 1: both centrings read the first ghost layer.
+        centering="cell": the sum over the components, in the order x, y, z,
+        of (V_d(+1 in d) - V_d(-1 in d)) * 0.5 * scale / dr_d with V_d at the
+        cells: the interior and the innermost ghost layer on the six faces are
+        read.  centering="face": of (V_d - V_d(-1 in d)) * scale / dr_d with
+        V_d(i) on the face between the cells i and i+1 along d, the layout
+        get_blocks_grad(centering="face") writes: the index along d from 0 to
+        nc is read.  Edges, corners and outer ghost layers are never read;
+        the ghost cells of iv keep their values.  Ordered on torch's current
+        stream: no host synchronisation.  With several ranks a call for phi
+        is collective (a rank with nothing passes n = 0).  Returns the number
+        of cells written."""
+        import torch
+        what = "set_blocks_div"
+        if centering not in ("cell", "face"):
+            raise ValueError(f"{what}: centering {centering!r}, 'cell' or 'face' is required")
+        if len(components) != 3:
+            raise ValueError(f"{what}: components takes three flags")
+        if int(ghost_width) < 1:
+            raise ValueError(f"{what}: ghost_width >= 1 is required")
+        if isinstance(blocks, torch.Tensor):
+            if blocks.dim() != 5 or blocks.shape[0] != 3:
+                raise ValueError(f"{what}: a torch tensor [3, box, k, j, i] is required")
+            parts = [blocks[d] for d in range(3)]
+        else:
+            parts = list(blocks)
+            if len(parts) != 3:
+                raise ValueError(f"{what}: three tensors (or None) are required")
+        parts = [t if components[d] else None for d, t in enumerate(parts)]
+        used = [t for t in parts if t is not None]
+        if not used:
+            raise ValueError(f"{what}: no component is given")
+        args = [self._blocks_args(t, ids, ghost_width, False, what) for t in used]
+        idl, off, stride, _ = args[0]
+        if any(t.shape != used[0].shape or t.stride() != used[0].stride() for t in used):
+            raise ValueError(f"{what}: the components differ in shape or strides")
+        if any(t.device != used[0].device for t in used):
+            raise ValueError(f"{what}: the components are on different devices")
+        return self.ctx.put_boxes_div(iv, idl, [0 if t is None else t.data_ptr() for t in parts], off, stride,
+                                      scale, int(centering == "face"),
+                                      torch.cuda.current_stream(used[0].device).cuda_stream)
+
     def _require_alloc(self):
         if not self.is_allocated:
             raise RuntimeError("allocate_storage: tree is not allocated")
