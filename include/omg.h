@@ -450,6 +450,58 @@ int omg_put_boxes_div(omg_ctx *ctx, int iv, int n_boxes, const int *ids,
                       const long long stride[3], double scale, int centering,
                       void *stream, long long *n_cells);
 
+/* omg_get_boxes_grad with an optional coefficient per component and an
+ * optional accumulate: the flux c_face * grad(iv) of the operators with a cell
+ * coefficient (D = -eps grad phi, u -= (1/rho) grad p, a heat flux), and the
+ * last step of a projection (B -= grad phi) as a read-modify-write of the
+ * host's pool.  ids, dev, box_off, stride, stream, n_cells, the plan-only
+ * behaviour, the ownership, range and "listed twice" checks, the stride rule
+ * (m = nc_max for cells, nc_max + 1 for faces), the elements touched per
+ * centring and the rule that everything else of a pool keeps its bits are
+ * exactly omg_get_boxes_grad's.
+ * iv_coef[d] is the coefficient variable of component d: 0 none, otherwise a
+ * variable 1..n_vars other than iv; iv_coef == NULL means {0, 0, 0}.
+ * Let g be omg_get_boxes_grad's value of an element, the same f_d and the
+ * same bits, (hi - lo) * f_d.  Then
+ *     iv_coef[d] == 0:   v = g;
+ *     centering == 1:    v = c * g,  c = ((2 * a_lo) * a_hi) / (a_lo + a_hi),
+ * a the coefficient in the cells lo and hi of the face along d: the
+ * reference's 2*a0*a/(a0+a) (src/m_vlaplacian.f90:84,152,
+ * src/m_ahelmholtz.f90:152,229) evaluated left to right, symmetric in the two
+ * cells, so two blocks that share a face get the same bits; it reads the
+ * coefficient's face ghosts at the index 0 and nc+1 along d;
+ *     centering == 0:    v = a(i,j,k) * g.
+ * accumulate == 0: dev[d][o] = v; accumulate != 0: dev[d][o] = dev[d][o] + v,
+ * one addition.  Every operation is rounded once, no contraction; signed
+ * zeros, Inf and NaN as IEEE gives them; a_lo + a_hi == 0 is the caller's
+ * affair.
+ * State: iv is read exactly as omg_get_boxes_grad reads it, fill included
+ * (collective on several ranks when set).  Each distinct coefficient variable
+ * is read as omg_get_boxes(..., fill = 0) reads it: pending work is applied
+ * and its ghosts are used as they stand, which is what the smoothers read.
+ * Nothing else of the state changes: a cycle after the call gives the bits it
+ * would have given without it.
+ * Errors (nothing is launched, no state is touched): omg_get_boxes_grad's,
+ * plus an iv_coef[d] out of range or equal to iv.  With accumulate each pool
+ * is checked over the same range as without it.
+ * The records and the cache key are the gradient's: a list that
+ * omg_get_boxes_grad cached serves this entry and the other way round;
+ * iv_coef, accumulate and scale are launch arguments, not part of the key.
+ * Kernels: a tile kernel for 16^3 and 8^3 boxes (the gradient's staging of
+ * iv in LDS; the coefficient read from the stored box by 16-B loads; 16-B or
+ * 8-B loads ahead of the stores when accumulating), a per-cell kernel for
+ * every other size and where it measured faster or nothing was measured: for
+ * a level of which fewer than 512 boxes are listed, and for cell centring;
+ * both give the same bits.
+ * OMG_BOXES_GENERIC=1 and OMG_BOXES_TILE=1 apply as they do to
+ * omg_get_boxes_grad.
+ * Profiling families: boxes_flux (the call), boxes_flux_tile (the tile
+ * kernel, per level). */
+int omg_get_boxes_flux(omg_ctx *ctx, int iv, const int iv_coef[3], int n_boxes, const int *ids,
+                       double *const dev[3], const long long *box_off, const long long stride[3],
+                       double scale, int centering, int accumulate, int fill,
+                       void *stream, long long *n_cells);
+
 /* The hot path.  omg_fas_vcycle = mg_fas_vcycle (src/m_multigrid.f90:150-243);
  * highest_lvl < lowest_lvl means "not present".  omg_fas_fmg = mg_fas_fmg
  * (:84-147).  max_res is written when want_max_res (the optional argument). */

@@ -541,6 +541,15 @@ int omg_put_boxes_div(omg_ctx* c, int iv, int n_boxes, const int* ids, const dou
   return guarded([&] { boxes_div(c, iv, n_boxes, ids, dev, box_off, stride, scale, centering, stream, n_cells); });
 }
 
+int omg_get_boxes_flux(omg_ctx* c, int iv, const int* iv_coef, int n_boxes, const int* ids, double* const* dev,
+                       const long long* box_off, const long long* stride, double scale, int centering, int accumulate,
+                       int fill, void* stream, long long* n_cells) {
+  return guarded([&] {
+    boxes_flux(c, iv, iv_coef, n_boxes, ids, dev, box_off, stride, scale, centering, accumulate != 0, fill != 0,
+               stream, n_cells);
+  });
+}
+
 int omg_fas_vcycle(omg_ctx* c, int highest_lvl, int want_max_res, double* max_res, int standalone) {
   return guarded([&] {
     const double r = run_cycle(c, 1 + (want_max_res ? 2 : 0) + 4 * (standalone != 0) + 8 * (highest_lvl + 64),

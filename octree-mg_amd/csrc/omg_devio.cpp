@@ -2,9 +2,11 @@
 // level's cell grid, kernels in omg_dense.hip), omg_get_dense_grad (the same
 // windows of a gradient, omg_dense_grad.hip), omg_put_boxes / omg_get_boxes
 // (block lists, omg_boxes.hip), omg_get_boxes_grad (the same lists of a
-// gradient, omg_boxes_grad.hip) and omg_put_boxes_div (the same lists from a
-// divergence, omg_boxes_div.hip): the caller's device memory, in the order of
-// the caller's stream, by cached records.  What the entries share stands first.
+// gradient, omg_boxes_grad.hip), omg_put_boxes_div (the same lists from a
+// divergence, omg_boxes_div.hip) and omg_get_boxes_flux (the gradient,
+// weighted and optionally added, omg_boxes_flux.hip): the caller's device
+// memory, in the order of the caller's stream, by cached records.  What the
+// entries share stands first.
 #include <algorithm>
 
 #include "omg_host.h"
@@ -647,6 +649,113 @@ void boxes_div(omg_ctx* c, int iv, int n_boxes, const int* ids, const double* co
                               c->stream);
       } else {
         launch_boxes_div_cell(V, iv, S.buf.d + G.first, G.n, A, stride[1], stride[2], centering != 0, c->stream);
+      }
+    }
+    HIPCHK(hipGetLastError());
+  }
+  join_out(c, stream);
+}
+
+// What tools/box_flux_bench.py measured for this entry's kernels (DESIGN §21,
+// profiles/r13/boxes_flux_bench.jsonl: 16^3 boxes, 128 .. 8000 listed boxes
+// of one level, face centring, no, one and three coefficients, writing and
+// accumulating, pools with one and two ghost layers).  The constants started
+// at "per-cell everywhere" (the sweep_* records) and moved only where the tile
+// kernel won by more than the rounds' spread (§14's rule).  Face centring: the
+// per-cell kernel won at 128 and 256 boxes in all twelve cases (1.1x to 1.6x);
+// the tile kernel won from 512 boxes on in every case but one tie (no
+// coefficient, writing, one ghost layer, 512 boxes: 0.0325 against 0.0346 ms,
+// inside the spread), 1.1x to 1.3x at 512, 1.2x to 1.7x from 1024 to 8000.
+// Cell centring was not timed: it stays with the per-cell kernel, and the
+// tile kernel runs there under OMG_BOXES_TILE=1 only.
+constexpr int kBoxesFluxTileMinCell = INT_MAX;
+constexpr int kBoxesFluxTileMinFace = 512;
+
+// omg_get_boxes_flux: omg_get_boxes_grad's checks, list, records, cache key
+// and stream ordering; a coefficient variable per component, read as a get
+// without a fill reads it, and an optional accumulate.
+void boxes_flux(omg_ctx* c, int iv, const int* iv_coef, int n_boxes, const int* ids, double* const* dev,
+                const long long* box_off, const long long* stride, double scale, int centering, bool accumulate,
+                bool fill, void* stream, long long* n_cells) {
+  const Fail fail{"omg_get_boxes_flux"};
+  if (iv < 1 || iv > c->n_vars) fail("bad variable index");
+  FluxCoef K{{0, 0, 0}};
+  for (int d = 0; d < 3 && iv_coef; d++) {
+    K.iv[d] = iv_coef[d];
+    if (K.iv[d] < 0 || K.iv[d] > c->n_vars)
+      fail("iv_coef[" + std::to_string(d) + "] = " + std::to_string(K.iv[d]) + " is not 0 or a variable 1.." +
+           std::to_string(c->n_vars));
+    if (K.iv[d] == iv) fail("iv_coef[" + std::to_string(d) + "] is iv itself");
+  }
+  if (centering != 0 && centering != 1) fail("centering must be 0 (cells) or 1 (faces)");
+  boxes_check_list(n_boxes, ids, box_off, stride, fail);
+  if (!dev) fail("the array of component pointers is required");
+  bool aligned = true, any = false;
+  for (int d = 0; d < 3; d++)
+    if (dev[d]) {
+      any = true;
+      aligned = aligned && ((uintptr_t)dev[d] & 15) == 0;
+      for (int e = 0; e < d; e++)
+        if (dev[e] == dev[d])
+          fail("components " + std::to_string(e) + " and " + std::to_string(d) + " share one pointer");
+    }
+  if (n_boxes > 0 && !any) fail("NULL pointers for all three components with n_boxes > 0");
+  if (c->levels.empty()) fail("no tree (omg_tree_setup)");
+  const bool generic = env_flag("OMG_BOXES_GENERIC"), force_tile = env_flag("OMG_BOXES_TILE");
+  // (the gradient's key: a list either entry cached serves both)
+  BoxPlan* P = boxes_cached(c, n_boxes, ids, box_off, stride, 0, centering, aligned);
+  BoxPlan fresh;
+  if (!P) {
+    fresh.centering = centering;
+    std::copy(stride, stride + 3, fresh.stride);
+    fresh.aligned = aligned;
+    boxes_build(c, fresh, n_boxes, ids, box_off, false, fail);
+  }
+  const BoxPlan& R = P ? *P : fresh;
+  if (n_boxes > 0) {
+    const long long m = R.nc_max + centering;
+    if (stride[1] < m) fail(centering ? "stride[1] < nc + 1" : "stride[1] < nc");
+    if (stride[2] / m < stride[1]) fail(centering ? "stride[2] < stride[1]*(nc + 1)" : "stride[2] < stride[1]*nc");
+  }
+  if (c->host_only) {
+    if (n_cells) *n_cells = R.n_cells;
+    return;
+  }
+  if (n_boxes > 0) {
+    // (the gradient's range, with and without accumulate)
+    for (int d = 0; d < 3; d++)
+      if (dev[d]) check_device_range(c, dev[d], R.lo_ext - (centering ? stride[d] : 0), R.hi_ext, "a block", fail);
+    for (const BoxGroup& G : R.groups)
+      if ((long long)G.n * 16 > INT_MAX) fail("too many boxes for one launch");
+  }
+  // --- nothing of the state was touched up to here
+  enter_get(c, iv, fill, c->lowest, c->highest);
+  // (each distinct coefficient as a get without a fill: its ghosts as they stand)
+  for (int d = 0; d < 3; d++)
+    if (K.iv[d] && std::find(K.iv, K.iv + d, K.iv[d]) == K.iv + d) enter_get(c, K.iv[d], false, c->lowest, c->highest);
+  if (n_cells) *n_cells = R.n_cells;
+  if (n_boxes == 0) return;
+  BoxPlan& S = boxes_claim(c, P, fresh);
+  join_in(c, stream);
+  {
+    Prof p(c, "boxes_flux", (double)S.n_cells);
+    for (const BoxGroup& G : S.groups) {
+      const Level* L = level_ptr(c, G.lvl);
+      const LevelView V = L->view();
+      DenseGrad A;
+      for (int d = 0; d < 3; d++) {
+        A.out[d] = dev[d];
+        A.f[d] = (centering ? scale : 0.5 * scale) / L->dr[d];
+      }
+      const bool measured = G.n >= (centering ? kBoxesFluxTileMinFace : kBoxesFluxTileMinCell);
+      const bool tile = !generic && boxes_tile_nc(L->nc) && (force_tile || measured);
+      if (tile) {
+        Prof pr(c, "boxes_flux_tile", (double)G.n * (L->nc + centering) * L->nc * L->nc, G.lvl);
+        launch_boxes_flux_tile(V, iv, S.buf.d + G.first, G.n, A, K, stride[1], stride[2], centering != 0, G.odd,
+                               accumulate, c->stream);
+      } else {
+        launch_boxes_flux_cell(V, iv, S.buf.d + G.first, G.n, A, K, stride[1], stride[2], centering != 0, accumulate,
+                               c->stream);
       }
     }
     HIPCHK(hipGetLastError());

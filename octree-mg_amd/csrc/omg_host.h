@@ -334,6 +334,9 @@ void boxes_grad(omg_ctx* c, int iv, int n_boxes, const int* ids, double* const* 
                 const long long* stride, double scale, int centering, bool fill, void* stream, long long* n_cells);
 void boxes_div(omg_ctx* c, int iv, int n_boxes, const int* ids, const double* const* dev, const long long* box_off,
                const long long* stride, double scale, int centering, void* stream, long long* n_cells);
+void boxes_flux(omg_ctx* c, int iv, const int* iv_coef, int n_boxes, const int* ids, double* const* dev,
+                const long long* box_off, const long long* stride, double scale, int centering, bool accumulate,
+                bool fill, void* stream, long long* n_cells);
 
 // --- omg_free_host.cpp
 void free_state_destroy(omg_ctx* c);

@@ -146,6 +146,12 @@ struct DenseGrad {
   double f[3];
 };
 
+// omg_get_boxes_flux's second kernel argument, beside a DenseGrad: the
+// coefficient variable of each component (0: the component is not weighted).
+struct FluxCoef {
+  int iv[3];
+};
+
 // omg_put_boxes_div's kernel argument: the component pools (null: the
 // component is skipped) and f_d = 0.5 * scale / dr_d (cells) or scale / dr_d
 // (faces).

@@ -239,6 +239,17 @@ void launch_boxes_div_tile(const LevelView& L, int iv, const BoxRec* recs, int n
                            long long s2, bool face, bool w8, hipStream_t st);
 void launch_boxes_div_cell(const LevelView& L, int iv, const BoxRec* recs, int n, const BoxDiv& G, long long s1,
                            long long s2, bool face, hipStream_t st);
+// omg_get_boxes_flux (omg_boxes_flux.hip): omg_get_boxes_grad's values g into
+// the same blocks, component d weighted by the coefficient variable K.iv[d]
+// (0: v = g): face = true: v = c * g with c = ((2 * a_lo) * a_hi) / (a_lo + a_hi)
+// over the face's two cells, ghosts as they stand; face = false: v = a * g with
+// the cell's own a.  acc: out = out + v instead of out = v.  The kernels take
+// what the gradient's take.
+void launch_boxes_flux_tile(const LevelView& L, int iv, const BoxRec* recs, int n, const DenseGrad& G,
+                            const FluxCoef& K, long long s1, long long s2, bool face, bool w8, bool acc,
+                            hipStream_t st);
+void launch_boxes_flux_cell(const LevelView& L, int iv, const BoxRec* recs, int n, const DenseGrad& G,
+                            const FluxCoef& K, long long s1, long long s2, bool face, bool acc, hipStream_t st);
 void launch_phi_bc_store(const LevelView& L, const GcBC& bc, int* nba, hipStream_t st);
 
 // The coarse end of the V-cycle in ONE single-workgroup launch (omg_tiles.hip):

@@ -54,6 +54,8 @@ SIGNATURES = {
                                 C.c_void_p, C.POINTER(_LL)]),
     "omg_put_boxes_div": (_I, [_P, _I, _I, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, _LP, _D, _I, C.c_void_p,
                                C.POINTER(_LL)]),
+    "omg_get_boxes_flux": (_I, [_P, _I, C.c_void_p, _I, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, _LP, _D, _I,
+                                _I, _I, C.c_void_p, C.POINTER(_LL)]),
     "omg_fas_vcycle": (_I, [_P, _I, _I, C.POINTER(_D), _I]),
     "omg_fas_fmg": (_I, [_P, _I, _I, C.POINTER(_D)]),
     "omg_apply_op": (_I, [_P, _I]),
@@ -364,6 +366,29 @@ class Context:
                   None if off is None else off.ctypes.data_as(C.c_void_p),
                   np.ascontiguousarray(stride, dtype=np.int64).reshape(3), float(scale), int(centering),
                   C.c_void_p(int(stream) or None), C.byref(cells))
+        return cells.value
+
+    def get_boxes_flux(self, iv, iv_coef, ids, ptrs, box_off, stride, scale=1.0, centering=0, accumulate=False,
+                       fill=True, stream=0):
+        """omg_get_boxes_flux: get_boxes_grad's values g, component d weighted
+        by the coefficient variable iv_coef[d] (0: v = g; None: no component
+        is weighted): centering 1: v = c * g with the harmonic mean
+        c = ((2 * a_lo) * a_hi) / (a_lo + a_hi) over the face's two cells,
+        centering 0: v = a * g with the cell's own a.  accumulate: the pools
+        become pool + v instead of v.  Returns the values per component."""
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        off = None if box_off is None else np.ascontiguousarray(box_off, dtype=np.int64).reshape(-1)
+        n = 0 if ids is None else ids.size
+        if off is not None and ids is not None and off.size != n:
+            raise ValueError(f"get_boxes_flux: {n} ids and {off.size} offsets")
+        coef = None if iv_coef is None else np.ascontiguousarray(iv_coef, dtype=np.int32).reshape(3)
+        dev = None if ptrs is None else (C.c_void_p * 3)(*[C.c_void_p(int(p or 0) or None) for p in ptrs])
+        cells = _LL(0)
+        self.call("get_boxes_flux", iv, None if coef is None else coef.ctypes.data_as(C.c_void_p), n,
+                  None if ids is None else ids.ctypes.data_as(C.c_void_p), dev,
+                  None if off is None else off.ctypes.data_as(C.c_void_p),
+                  np.ascontiguousarray(stride, dtype=np.int64).reshape(3), float(scale), int(centering),
+                  int(bool(accumulate)), int(bool(fill)), C.c_void_p(int(stream) or None), C.byref(cells))
         return cells.value
 
     def scalar(self, name, *args):

@@ -19,7 +19,7 @@ module m_omg_capi
   public :: omg_level_size, omg_upload_level, omg_download_level
   public :: omg_put_dense, omg_get_dense, omg_get_dense_grad
   public :: omg_put_boxes, omg_get_boxes, omg_get_boxes_grad
-  public :: omg_put_boxes_div
+  public :: omg_put_boxes_div, omg_get_boxes_flux
   public :: omg_fas_vcycle, omg_fas_fmg, omg_apply_op, omg_phi_bc_store
   public :: omg_synchronize, omg_diffusion_solve
   public :: omg_poisson_free_3d, omg_free_planes
@@ -273,6 +273,23 @@ module m_omg_capi
        type(c_ptr), value               :: stream, n_cells
        integer(c_int) :: ierr
      end function omg_put_boxes_div
+
+     ! omg_get_boxes_flux (include/omg.h): omg_get_boxes_grad's arguments with
+     ! iv_coef, the coefficient variable of each component (0: none), and
+     ! accumulate (dev = dev + value) by value
+     function omg_get_boxes_flux(ctx, iv, iv_coef, n_boxes, ids, dev, box_off, stride, scale, centering, &
+          accumulate, fill, stream, n_cells) bind(C, name="omg_get_boxes_flux") result(ierr)
+       import :: c_ptr, c_int, c_long_long, c_double
+       type(c_ptr), value               :: ctx
+       integer(c_int), value            :: iv, n_boxes
+       integer(c_int), intent(in)       :: iv_coef(3), ids(*)
+       type(c_ptr), intent(in)          :: dev(3)
+       integer(c_long_long), intent(in) :: box_off(*), stride(3)
+       real(c_double), value            :: scale
+       integer(c_int), value            :: centering, accumulate, fill
+       type(c_ptr), value               :: stream, n_cells
+       integer(c_int) :: ierr
+     end function omg_get_boxes_flux
 
      function omg_fas_vcycle(ctx, highest_lvl, want_max_res, max_res, standalone) &
           bind(C, name="omg_fas_vcycle") result(ierr)

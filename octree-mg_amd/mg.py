@@ -368,6 +368,99 @@ class MG(MGTree):
                                         torch.cuda.current_stream(used[0].device).cuda_stream)
         return out, cells
 
+    def flux_coefficients(self, coef=None):
+        """The coefficient variables (x, y, z; 0: none) get_blocks_flux uses.
+        coef=None: the operator's own, by operator_type: none for the
+        Laplacian and Helmholtz operators, (5, 5, 5) for the variable-
+        coefficient ones (eps in variable 5), (5, 6, 7) for the anisotropic
+        one.  Otherwise one variable for all three components, or a sequence
+        of three, 0 or None meaning none."""
+        if coef is None:
+            if self.operator_type in (MG_VLAPLACIAN, MG_VHELMHOLTZ):
+                return (5, 5, 5)
+            if self.operator_type == MG_AHELMHOLTZ:
+                return (5, 6, 7)
+            if self.operator_type in (MG_LAPLACIAN, MG_HELMHOLTZ):
+                return (0, 0, 0)
+            raise ValueError("get_blocks_flux: unknown operator")
+        if isinstance(coef, (int, np.integer)) and not isinstance(coef, bool):
+            return (int(coef),) * 3
+        try:
+            vals = tuple(0 if v is None else int(v) for v in coef)
+        except TypeError:
+            raise ValueError(f"get_blocks_flux: coef {coef!r}, a variable or a sequence of three is required") from None
+        if len(vals) != 3:
+            raise ValueError("get_blocks_flux: coef takes one variable or three")
+        return vals
+
+    def get_blocks_flux(self, ids, iv=1, coef=None, out=None, ghost_width=0, scale=1.0, fill=True, centering="face",
+                        accumulate=False, components=(True, True, True)):
+        """omg_get_boxes_flux: get_blocks_grad's values, each component
+        weighted by a coefficient variable and optionally added to `out`;
+        `out`, its forms and its layout checks are get_blocks_grad's.  With g
+        the gradient's value of an element:
+        centering="face" (the default; ghost_width >= 1): v = c * g with
+        c = ((2 * a_lo) * a_hi) / (a_lo + a_hi), the harmonic mean of the
+        coefficient in the face's two cells, the face weight of the operators
+        with a cell coefficient, so that the face-centred divergence of the
+        result (set_blocks_div) is what the solver inverted; the coefficient's
+        face ghosts are read as they stand.  centering="cell": v = a * g with
+        the cell's own coefficient.  A component without a coefficient: v = g.
+        coef: see flux_coefficients; None takes the operator's own.
+        accumulate=True: out = out + v (out is required), e.g. scale=-1.0 for
+        the correction B -= grad(phi) of a projection in one pass.  fill: the
+        ghost cells of iv are filled first on every level (collective on
+        several ranks); the coefficients are never filled.  Ordered on torch's
+        current stream.  Returns (out, values per component)."""
+        import torch
+        what = "get_blocks_flux"
+        if centering not in ("cell", "face"):
+            raise ValueError(f"{what}: centering {centering!r}, 'cell' or 'face' is required")
+        if len(components) != 3:
+            raise ValueError(f"{what}: components takes three flags")
+        if centering == "face" and int(ghost_width) < 1:
+            raise ValueError(f"{what}: centering='face' needs ghost_width >= 1")
+        if accumulate and out is None:
+            raise ValueError(f"{what}: accumulate=True needs `out`")
+        iv_coef = self.flux_coefficients(coef)
+        n_vars = self.n_vars
+        for v in iv_coef:
+            if v < 0 or v > n_vars or v == iv:
+                raise ValueError(f"{what}: coefficient variable {v}: 0 or a variable 1..{n_vars} other than iv = {iv} "
+                                 "is required")
+        if out is None:
+            self._require_alloc()
+            idl = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+            sizes = {int(self.box_size_lvl[int(l)]) for l in np.unique(self.lvl[idl])} if len(idl) else {0}
+            if len(sizes) > 1:
+                raise ValueError(f"{what}: the listed boxes have the box sizes {sorted(sizes)}, one is required")
+            m = sizes.pop() + 2 * int(ghost_width)
+            dev = self.ctx.device
+            out = torch.empty((3, len(idl), m, m, m), dtype=torch.float64,
+                              device=torch.device("cuda", dev if dev >= 0 else torch.cuda.current_device()))
+        if isinstance(out, torch.Tensor):
+            if out.dim() != 5 or out.shape[0] != 3:
+                raise ValueError(f"{what}: a torch tensor [3, box, k, j, i] is required")
+            parts = [out[d] for d in range(3)]
+        else:
+            parts = list(out)
+            if len(parts) != 3:
+                raise ValueError(f"{what}: three tensors (or None) are required")
+        parts = [t if components[d] else None for d, t in enumerate(parts)]
+        used = [t for t in parts if t is not None]
+        if not used:
+            raise ValueError(f"{what}: no component is asked for")
+        args = [self._blocks_args(t, ids, ghost_width, False, what) for t in used]
+        idl, off, stride, _ = args[0]
+        if any(t.shape != used[0].shape or t.stride() != used[0].stride() for t in used):
+            raise ValueError(f"{what}: the components differ in shape or strides")
+        if any(t.device != used[0].device for t in used):
+            raise ValueError(f"{what}: the components are on different devices")
+        cells = self.ctx.get_boxes_flux(iv, iv_coef, idl, [0 if t is None else t.data_ptr() for t in parts], off,
+                                        stride, scale, int(centering == "face"), bool(accumulate), fill,
+                                        torch.cuda.current_stream(used[0].device).cuda_stream)
+        return out, cells
+
     def set_blocks_div(self, iv, blocks, ids, ghost_width, scale=1.0, centering="cell",
                        components=(True, True, True)):
         """omg_put_boxes_div: variable iv of the boxes `ids` (as set_blocks lists
