@@ -283,6 +283,10 @@ int omg_get_dense_grad(omg_ctx *ctx, int lvl, int iv, double *const dev[3],
  * every rank calls it, with n_boxes == 0 where it has nothing.  ghost == 0
  * leaves the ghost slots alone (a put into rhs keeps what omg_phi_bc_store
  * stored there); ghost == 1 writes the face slots as omg_upload_level does.
+ * After omg_phi_bc_store those slots of rhs hold phi's boundary values: a put
+ * of rhs with ghost == 1 (like an upload of rhs, a fill of rhs or
+ * omg_subtract_mean of rhs with its ghosts) then makes the phi ghosts of every
+ * level stale too, and is collective as a put of phi is.
  * A box on a replicated level is refused (use omg_upload_level).
  * State, omg_get_boxes: reads like omg_download_level (pending shifts are
  * applied, deferred ghosts filled and a pending res formed before anything is

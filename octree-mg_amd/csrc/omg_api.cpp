@@ -453,6 +453,7 @@ int omg_upload_level(omg_ctx* c, int lvl, int iv, const double* host) {
     // (before the early return: a rank without boxes here still drops the
     // flag, which the multi-rank stand-alone fill decision relies on)
     if (iv == 1) phi_dirty(c, lvl);
+    if (iv == 2) rhs_ghosts_written(c, lvl);   // (the upload writes the ghost slots too)
     if (!L->n) return;
     const size_t s = L->nc + 2, box = s * s * s, n = box * L->n;
     double* st = stage(c, n);

@@ -106,6 +106,7 @@ void fill_gc_lvl(omg_ctx* c, int lvl, int iv) {
     ready(c, lvl, kWrite);
     wrote(c, lvl, kGcAll);
   }
+  if (iv == 2) rhs_ghosts_written(c, lvl);
   if (L->n) {
     Prof p(c, "fill_gc", (double)L->n * 6 * L->nc * L->nc, lvl);
     if (iv != 1 || L->has_rb || c->no_fill_tile ||

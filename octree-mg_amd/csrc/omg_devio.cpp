@@ -441,6 +441,7 @@ void box_io(omg_ctx* c, int iv, int n_boxes, const int* ids, double* dev, const 
     // (every level: a rank cannot know which levels its peers list, and the
     // stand-alone fill decision must fall alike on every rank)
     if (iv == 1) phi_dirty_all(c);
+    if (iv == 2 && ghost) rhs_ghosts_written_all(c);
   } else {
     enter_get(c, iv, fill, c->lowest, c->highest);
   }

@@ -276,6 +276,9 @@ double* other_phi(const Level* L);
 void rb_stale_above(omg_ctx* c, int lvl);
 void phi_dirty(omg_ctx* c, int lvl);
 void phi_dirty_all(omg_ctx* c);
+// rhs's ghost slots were written: phi's ghosts are stale where they hold mg_phi_bc_store's data
+void rhs_ghosts_written(omg_ctx* c, int lvl);
+void rhs_ghosts_written_all(omg_ctx* c);
 // (dead_lvl: that level's cycle overwrites its res, a pending one is dropped)
 void materialize_res_all(omg_ctx* c, int dead_lvl = INT_MIN);
 bool res_pend_ok(omg_ctx* c, const Level* L);

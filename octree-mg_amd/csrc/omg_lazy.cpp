@@ -26,6 +26,17 @@ void phi_dirty(omg_ctx* c, int lvl) {
 void phi_dirty_all(omg_ctx* c) {
   for (auto& kv : c->levels) kv.second.phi_gc_ok = kv.second.rbgv_ok = kv.second.gc_deferred = false;
 }
+// After mg_phi_bc_store phi's boundary values live in rhs's ghost slots, and
+// phi's ghosts across physical faces are formed from them (GcBC::phi_stored):
+// a write of those slots (an upload or a put of rhs with its ghosts, a fill of
+// rhs, subtract_mean with the ghosts) makes phi's ghosts stale, as a fill
+// after it would change them.
+void rhs_ghosts_written(omg_ctx* c, int lvl) {
+  if (c->phi_bc_data_stored) phi_dirty(c, lvl);
+}
+void rhs_ghosts_written_all(omg_ctx* c) {
+  if (c->phi_bc_data_stored) phi_dirty_all(c);
+}
 
 // --- the unstored res (Level::res_pend)
 static void materialize_res(omg_ctx* c, Level* L) {

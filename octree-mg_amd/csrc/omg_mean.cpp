@@ -203,6 +203,7 @@ void subtract_mean(omg_ctx* c, int iv, int ghosts, int mode) {
     // (phi of every level changes: the refinement-boundary coarse parts the
     // level above stored, Level::rbgv_ok, are those of the old phi)
     if (L && iv == 1) L->rbgv_ok = false;
+    if (L && iv == 2 && ghosts) rhs_ghosts_written(c, l);
     if (L && L->n) {
       Prof p(c, "subtract", (double)L->n * L->nc * L->nc * L->nc, l);
       launch_subtract(L->view(), iv, red_mean(c, ch), ghosts, c->stream);

@@ -27,15 +27,26 @@ Steps are tuples, the kind first:
   ("bc", nb, type, value)               omg_set_bc of phi, one face
   ("phi_bc_store",)
 
+and, for the device I/O entries (torch tensors on the device's side, numpy on
+get_level / set_level on the oracle's; `sel` names a list of boxes, devio_ids):
+
+  ("put_dense", lvl, iv, win) / ("get_dense", lvl, iv, win)     win: "whole" | "cut"
+  ("get_dense_grad", lvl, iv, win, scale, fill)
+  ("put_boxes", sel, iv, ghosts) / ("get_boxes", sel, iv, ghosts, fill)
+  ("get_boxes_grad", sel, iv, centering, scale, fill)
+  ("put_boxes_div", sel, iv, centering, scale)
+  ("get_boxes_flux", sel, iv, centering, scale, fill, coef, accumulate)
+
 The generator (walk) draws only calls that are legal on the tree: the oracle
 abort()s where the reference has an error stop (prolong of the highest level,
 restriction of the lowest).
 
 The lists are sized by the oracle's wall time (a few seconds per case at the
-most), recorded in tests/test_gpu_api_walk.py.
+most), recorded in tests/test_gpu_api_walk.py and tests/test_gpu_devio_walk.py.
 """
 import hashlib
 import random
+import zlib
 
 import numpy as np
 
@@ -125,11 +136,19 @@ class Methods:
         mg._push_methods()
 
 
-def apply_step(be, meth, step, src=None):
+def apply_step(be, meth, step, src=None, rec=None, msg=None):
     """One step on one backend; the scalar the call returns, or None.  src:
-    the backend an upload takes its data from (the same cells on either)."""
+    the backend an upload takes its data from (the same cells on either).
+    rec: the record of a device I/O step, written by the oracle's half and
+    read by the device's (devio_oracle, devio_device)."""
     kind, a = step[0], step[1:]
     src = be if src is None else src
+    if kind in DEVIO_KINDS:
+        if _is_oracle(be):
+            devio_oracle(be, step, rec)
+        else:
+            devio_device(be, step, rec, msg)
+        return None
     if kind == "vcycle":
         return be.vcycle(a[0])
     if kind == "vcycle_to":
@@ -191,7 +210,8 @@ class Pair:
     """The device and the oracle over one problem, given every change alike.
     device=False: the oracle alone (the walks' legality, on a CPU)."""
 
-    def __init__(self, args, device=True):
+    def __init__(self, args, device=True, devio=False):
+        """devio: variable 5 holds get_boxes_flux's coefficient (devio_setup)."""
         self.cfg = cfg = parse(args)
         self.orc = OracleBackend(cfg)
         self.dev = DeviceBackend(cfg) if device else None
@@ -200,6 +220,8 @@ class Pair:
         for be in (self.dev, self.orc):
             if be is not None:
                 setup_problem(be)
+                if devio:
+                    devio_setup(be)
 
     def set(self, cycles=None, coarse=None, oracle_cycles=None):
         if cycles is not None:
@@ -222,9 +244,10 @@ class Pair:
                         be.set_level(lvl, iv, a)
             return
         # (a change of the settings is made in self.meth twice, to the same values)
-        r_orc = apply_step(self.orc, self.meth, step)
+        rec = {}   # (a device I/O step: what the oracle's half leaves for the device's)
+        r_orc = apply_step(self.orc, self.meth, step, rec=rec)
         if self.dev is not None:
-            r_dev = apply_step(self.dev, self.meth, step)
+            r_dev = apply_step(self.dev, self.meth, step, rec=rec, msg=msg)
             assert r_dev == r_orc, (r_dev, r_orc, msg)
 
     def run(self, steps, lazy=False, skip=()):
@@ -438,15 +461,403 @@ def checkpoint(be, out, n, ids_of=None):
                 out[(n, lvl, int(id_), iv)] = hashlib.sha256(a[q].tobytes()).digest()
 
 
-def run_rank(be, steps, lazy=False):
+def run_rank(be, steps, lazy=False, recs=None, skip=()):
     """A rank's (or the oracle's) run of a step list: ({step: scalar},
-    {(step, lvl, id, iv): digest}); every rank makes the same calls."""
+    {(step, lvl, id, iv): digest}); every rank makes the same calls.  recs:
+    {step: record} of the device I/O steps, filled by the oracle's run (made
+    first) and read by every rank's.  skip: kinds of step that no checkpoint
+    follows (Pair.run's)."""
     meth = Methods(be.cfg)
     scalars, boxes = {}, {}
     for n, step in enumerate(steps):
-        r = apply_step(be, meth, step)
+        rec = None if recs is None else recs.setdefault(n, {})
+        r = apply_step(be, meth, step, rec=rec, msg=f"step {n} {step} of {steps}")
         if r is not None:
             scalars[n] = r
+        if step[0] in skip and n + 1 < len(steps):
+            continue
         if not (lazy and _lazy_skip(step) and n + 1 < len(steps)):
             checkpoint(be, boxes, n)
     return scalars, boxes
+
+
+# -- the device I/O entries ---------------------------------------------------------
+# omg_put_dense, omg_get_dense, omg_get_dense_grad, omg_put_boxes, omg_get_boxes,
+# omg_get_boxes_grad, omg_put_boxes_div, omg_get_boxes_flux.  A step has two
+# halves.  The oracle's comes first: numpy on get_level / set_level (and the
+# oracle's fill where the device call has fill=True), with the restatements the
+# entries' own tests check them by; it leaves a record (the data of a put, the
+# boxes a get reads).  The device's makes the call through the MG mirrors with
+# torch tensors built from the record, and compares what a get returns, and
+# every count, with numpy's on the record.  What a put stored is compared by
+# the comparison of all stored cells that follows the step.
+DEVIO_KINDS = ["put_dense", "get_dense", "get_dense_grad", "put_boxes", "get_boxes", "get_boxes_grad",
+               "put_boxes_div", "get_boxes_flux"]
+DEVIO_PUTS = ("put_dense", "put_boxes", "put_boxes_div")
+DEVIO_SEED = 20261021
+I_COEF = 5   # the spare variable of the Laplacian and Helmholtz trees: the flux's coefficient
+
+
+def _restatements():
+    """numpy's statements of the entries, from the modules that test each
+    entry alone (imported late: they import this module)."""
+    from tests import denseutil as U
+    from tests import test_gpu_boxes_div as BD
+    from tests import test_gpu_boxes_flux as BF
+    from tests import test_gpu_boxes_grad as BG
+    from tests import test_gpu_dense_grad as DG
+    return U, BG, BD, BF, DG
+
+
+def _step_rng(step, salt=0):
+    return np.random.default_rng([DEVIO_SEED, zlib.crc32(repr(step).encode()), salt])
+
+
+def _rows(be, lvl, ids):
+    """The rows of the listed boxes in the level's array as get_level orders it."""
+    pos = {int(i): q for q, i in enumerate(be.tree.lvls[lvl].ids)}
+    return [pos[int(i)] for i in ids]
+
+
+def devio_setup(be):
+    """Variable 5 on every level: a coefficient in [0.5, 2], ghosts included
+    (test_gpu_boxes_flux._random_coef), the same for a box on either backend
+    and on whichever rank owns it."""
+    _, _, _, BF, _ = _restatements()
+    tree = be.tree
+    for lvl in be.levels():
+        n = len(tree.lvls[lvl].ids)
+        a = BF._random_coef(np.random.default_rng([DEVIO_SEED, lvl + 64]), n, tree.box_size_lvl[lvl])
+        _put(be, lvl, I_COEF, a[_rows(be, lvl, be.my_ids(lvl))])
+
+
+def devio_ids(tree, sel):
+    """The boxes a selector names, of the whole tree (a rank lists its own of
+    them, in this order): ("perm", lvl, seed) a level's ids in a permuted
+    order, ("subset", lvl, seed) the first half of such an order, ("leaves",)
+    every leaf of the levels >= 1, ("slab", lvl) the level's lowest z-slab."""
+    if sel[0] == "leaves":
+        return [int(i) for l in range(1, tree.highest_lvl + 1) for i in tree.lvls[l].leaves]
+    ids = [int(i) for i in tree.lvls[sel[1]].ids]
+    if sel[0] == "slab":
+        return [i for i in ids if int(tree.ix[i][2]) == 1]
+    ids = [ids[q] for q in np.random.default_rng([DEVIO_SEED, sel[2]]).permutation(len(ids))]
+    return ids[:(len(ids) + 1) // 2] if sel[0] == "subset" and len(ids) > 1 else ids
+
+
+def devio_window(tree, lvl, win):
+    """(lo, n) of a dense window: the level's whole grid, or one that cuts
+    through its boxes (denseutil.cut_windows)."""
+    from tests import denseutil as U
+    if win == "whole":
+        return [0, 0, 0], list(U.grid(tree, lvl))
+    return U.cut_windows(tree, lvl)[0]
+
+
+def _by_level(tree, ids):
+    """{lvl: positions in the list} of a list of boxes."""
+    out = {}
+    for q, i in enumerate(ids):
+        out.setdefault(int(tree.lvl[i]), []).append(q)
+    return out
+
+
+def _noisy(rng, old):
+    """Half of the values plus noise of 1e-3 of their magnitude."""
+    s = float(np.abs(old).max()) if old.size else 0.0
+    return 0.5 * old + (1e-3 * (s or 1.0)) * rng.standard_normal(old.shape)
+
+
+def _cell_masks(nc):
+    """(interior, interior and the six face layers) of a (nc+2)^3 box."""
+    from tests import denseutil as U
+    inner = np.zeros((nc + 2,) * 3, dtype=bool)
+    inner[1:-1, 1:-1, 1:-1] = True
+    return inner, U.stored_mask(nc)
+
+
+def devio_oracle(orc, step, rec):
+    """The oracle's half of a device I/O step, and its record in rec."""
+    U, BG, BD, BF, DG = _restatements()
+    kind, a = step[0], step[1:]
+    tree = orc.tree
+    rng = _step_rng(step)
+    if kind in ("put_dense", "get_dense", "get_dense_grad"):
+        lvl, iv, win = a[:3]
+        if kind == "get_dense_grad" and a[4]:   # (a dense entry fills the one level)
+            orc.call("fill_ghost_cells_lvl", lvl, iv)
+        old = orc.get_level(lvl, iv)
+        lo, n = devio_window(tree, lvl, win)
+        if kind != "put_dense":
+            rec["src"] = {lvl: old}
+            return
+        ids = tree.lvls[lvl].ids
+        full = U.assemble(tree, lvl, ids, _noisy(rng, old), U.SENTINEL)
+        rec["dense"] = np.ascontiguousarray(DG._crop(full[None], lo, n)[0]).view(np.float64)
+        orc.set_level(lvl, iv, U.scatter(tree, lvl, ids, old, rec["dense"], lo))
+        return
+    sel, iv = a[:2]
+    ids = rec["ids"] = devio_ids(tree, sel)
+    groups = _by_level(tree, ids)
+    nc = tree.box_size_lvl[next(iter(groups))]
+    assert {tree.box_size_lvl[l] for l in groups} == {nc}
+    inner, stored = _cell_masks(nc)
+    if kind == "put_boxes":
+        mask = stored if a[2] else inner   # (the cells the entry defines: the others keep the last fill's values)
+        blocks = np.full((len(ids),) + (nc + 2,) * 3, U.SENTINEL, dtype=np.int64).view(np.float64)
+        for lvl, qs in sorted(groups.items()):
+            old = orc.get_level(lvl, iv)
+            rows = _rows(orc, lvl, [ids[q] for q in qs])
+            part = old[rows]
+            part[:, mask] = _noisy(rng, part)[:, mask]
+            blocks[np.asarray(qs)[:, None], mask] = part[:, mask]
+            old[rows] = part
+            orc.set_level(lvl, iv, old)
+        rec["blocks"] = blocks
+    elif kind == "put_boxes_div":
+        centering, scale = a[2:]
+        field = np.zeros((3, len(ids)) + (nc + 2,) * 3)
+        for lvl, qs in sorted(groups.items()):
+            # (a field of the size of the mesh width: a divergence of order one on every level)
+            v = BD._field(rng, len(qs), nc + 2) * float(np.min(tree.dr[lvl]))
+            field[:, qs] = v
+            old = orc.get_level(lvl, iv)
+            rows = _rows(orc, lvl, [ids[q] for q in qs])
+            part = old[rows]
+            part[:, 1:-1, 1:-1, 1:-1] = BD.block_div(v, nc, 1, tree.dr[lvl], scale, centering)
+            old[rows] = part
+            orc.set_level(lvl, iv, old)
+        rec["field"] = BD._poison(field, nc, 1, centering, (True, True, True))
+    else:
+        fill = {"get_boxes": 3, "get_boxes_grad": 4, "get_boxes_flux": 4}[kind]
+        if a[fill]:   # (a block entry fills every level)
+            orc.fill_ghost_cells(iv)
+        rec["src"] = {lvl: orc.get_level(lvl, iv) for lvl in groups}
+        if kind == "get_boxes_flux" and a[5]:
+            rec["coef"] = {lvl: orc.get_level(lvl, a[5]) for lvl in groups}
+
+
+def devio_expected(be, step, rec, ids=None):
+    """(bits a get's output starts as, bits it must hold after the call, the
+    count the call must return), numpy's on the oracle's record.  ids: the
+    boxes listed (a rank's own of the selection; a dense entry: the rank's
+    boxes of the level), default the oracle's: all of them."""
+    U, BG, BD, BF, DG = _restatements()
+    kind, a = step[0], step[1:]
+    tree = be.tree
+    if kind in ("get_dense", "get_dense_grad"):
+        lvl, iv, win = a[:3]
+        lo, n = devio_window(tree, lvl, win)
+        ids = tree.lvls[lvl].ids if ids is None else ids
+        boxes = rec["src"][lvl][_rows(be, lvl, ids)]
+        if kind == "get_dense":
+            want = DG._crop(U.assemble(tree, lvl, ids, boxes, U.SENTINEL)[None], lo, n)[0]
+        else:
+            want = DG._crop(DG.numpy_grad(tree, lvl, ids, boxes, a[3]), lo, n)
+        return np.full(want.shape, U.SENTINEL, dtype=np.int64), want, U.count_cells(tree, lvl, lo, n, ids)
+    ids = rec["ids"] if ids is None else ids
+    groups = _by_level(tree, ids)
+    nc = tree.box_size_lvl[int(tree.lvl[rec["ids"][0]])]
+    shape = (len(ids),) + (nc + 2,) * 3
+    inner, stored = _cell_masks(nc)
+    if kind == "get_boxes":
+        mask = stored if a[2] else inner
+        base = np.full(shape, U.SENTINEL, dtype=np.int64)
+        want = base.copy()
+        for lvl, qs in groups.items():
+            boxes = rec["src"][lvl][_rows(be, lvl, [ids[q] for q in qs])]
+            want[np.asarray(qs)[:, None], mask] = boxes.view(np.int64)[:, mask]
+        return base, want, len(ids) * int(mask.sum())
+    centering, scale = a[2:4]
+    acc = kind == "get_boxes_flux" and bool(a[6])
+    # (accumulating: finite random bits, a NaN's payload after an addition is not IEEE's to define)
+    base = BF._random_bits(_step_rng(step, 1), (3,) + shape) if acc else np.full((3,) + shape, U.SENTINEL, np.int64)
+    want = base.copy()
+    per_box = 0
+    for lvl, qs in groups.items():
+        rows = _rows(be, lvl, [ids[q] for q in qs])
+        boxes = rec["src"][lvl][rows]
+        if kind == "get_boxes_grad":
+            bits, mask = BG.block_grad(boxes, tree.dr[lvl], scale, centering)
+            want[:, qs] = BG.in_pool(bits, mask, 1)
+        else:
+            coefs = [rec["coef"][lvl][rows]] * 3 if a[5] else [None] * 3
+            vals, mask = BF.block_flux(boxes, coefs, tree.dr[lvl], scale, centering)
+            want[:, qs] = BF.in_blocks(vals, mask, 1, base[:, qs], acc)
+        per_box = int(mask[0].sum())
+    return base, want, len(ids) * per_box
+
+
+def devio_device(dev, step, rec, msg=None):
+    """The device's half of a device I/O step: the call through the MG mirror
+    on torch tensors, this rank's boxes of the step's selection; the count it
+    returns and, of a get, every bit of the output against numpy's."""
+    import torch
+    U = _restatements()[0]
+    kind, a = step[0], step[1:]
+    mg, tree = dev.mg, dev.tree
+
+    def cuda(x):
+        return torch.from_numpy(np.ascontiguousarray(x)).cuda()
+
+    def same(out, want, n, count):
+        assert n == count, (n, count, msg)
+        got = np.ascontiguousarray(out.cpu().numpy()).view(np.int64)
+        assert np.array_equal(got, want), msg
+
+    if kind in ("put_dense", "get_dense", "get_dense_grad"):
+        lvl, iv, win = a[:3]
+        lo, n = devio_window(tree, lvl, win)
+        ids = dev.my_ids(lvl)
+        if kind == "put_dense":
+            cells = mg.set_dense(lvl, iv, cuda(rec["dense"]), lo)
+            assert cells == U.count_cells(tree, lvl, lo, n, ids), (cells, msg)
+            return
+        base, want, count = devio_expected(dev, step, rec, ids)
+        out = cuda(base).view(torch.float64)
+        if kind == "get_dense":
+            _, cells = mg.get_dense(lvl, iv, out=out, lo=lo)
+        else:
+            _, cells = mg.get_dense_grad(lvl, iv, out=out, lo=lo, scale=a[3], fill=bool(a[4]))
+        same(out, want, cells, count)
+        return
+    sel, iv = a[:2]
+    where = [q for q, i in enumerate(rec["ids"]) if int(tree.rank[i]) == tree.my_rank]
+    ids = [rec["ids"][q] for q in where]
+    if kind == "put_boxes":
+        cells = mg.set_blocks(iv, cuda(rec["blocks"][where]), ids, ghost_width=1, ghosts=bool(a[2]))
+        inner, stored = _cell_masks(rec["blocks"].shape[1] - 2)
+        assert cells == len(ids) * int((stored if a[2] else inner).sum()), (cells, msg)
+    elif kind == "put_boxes_div":
+        cells = mg.set_blocks_div(iv, cuda(rec["field"][:, where]), ids, 1, scale=a[3], centering=a[2])
+        assert cells == len(ids) * (rec["field"].shape[2] - 2) ** 3, (cells, msg)
+    else:
+        base, want, count = devio_expected(dev, step, rec, ids)
+        out = cuda(base).view(torch.float64)
+        if kind == "get_boxes":
+            _, cells = mg.get_blocks(iv, ids, out=out, ghost_width=1, ghosts=bool(a[2]), fill=bool(a[3]))
+        elif kind == "get_boxes_grad":
+            _, cells = mg.get_blocks_grad(ids, iv, out=out, ghost_width=1, scale=a[3], fill=bool(a[4]),
+                                          centering=a[2])
+        else:
+            _, cells = mg.get_blocks_flux(ids, iv, coef=a[5], out=out, ghost_width=1, scale=a[3], fill=bool(a[4]),
+                                          centering=a[2], accumulate=bool(a[6]))
+        same(out, want, cells, count)
+
+
+def devio_directed_kinds(cfg, lo, hi):
+    """One list of fixed argument choices over the eight entries: every
+    variable an entry takes, both centrings, the three scales, fill and
+    accumulate off and on, with and without the coefficient, the four kinds of
+    block list and both dense windows."""
+    perm, sub, low = ("perm", hi, 1), ("subset", hi, 2), ("perm", lo + 2, 4)   # (lo + 2: boxes of 8 cells)
+    leaves = ("leaves",) if cfg["n_levels"] > 1 else ("perm", hi, 3)
+    return [("put_dense", hi, 1, "whole"), ("put_dense", hi, 2, "cut"),
+            ("get_dense", hi, 1, "cut"), ("get_dense", hi, 2, "whole"), ("get_dense", hi, 4, "whole"),
+            ("get_dense_grad", hi, 1, "whole", -1.0, True), ("get_dense_grad", hi, 2, "cut", 0.37, False),
+            ("get_dense_grad", hi, 4, "cut", 1.0, False),
+            ("put_boxes", perm, 1, True), ("put_boxes", sub, 1, False), ("put_boxes", leaves, 2, False),
+            ("put_boxes", low, 2, True),
+            ("get_boxes", sub, 1, True, True), ("get_boxes", perm, 2, True, False),
+            ("get_boxes", leaves, 4, False, False), ("get_boxes", low, 1, True, False),
+            ("get_boxes_grad", perm, 1, "face", -1.0, True), ("get_boxes_grad", sub, 1, "cell", 0.37, False),
+            ("get_boxes_grad", leaves, 2, "face", 1.0, False), ("get_boxes_grad", low, 4, "cell", -1.0, False),
+            ("put_boxes_div", perm, 2, "face", 1.0), ("put_boxes_div", sub, 1, "cell", -1.0),
+            ("put_boxes_div", leaves, 1, "face", 0.37),
+            ("get_boxes_flux", perm, 1, "face", -1.0, True, I_COEF, True),
+            ("get_boxes_flux", sub, 1, "cell", 1.0, False, 0, False),
+            ("get_boxes_flux", leaves, 2, "face", 0.37, False, I_COEF, False),
+            ("get_boxes_flux", low, 4, "cell", -1.0, True, 0, True)]
+
+
+def _draw_devio(rng, kind, cfg, lo, hi):
+    """A legal argument choice of one device I/O kind."""
+    r = rng.randrange
+
+    def sel():
+        what = rng.choice(["perm", "subset", "leaves", "coarse"])
+        if what == "leaves":
+            return ("leaves",) if cfg["n_levels"] > 1 else ("perm", hi, r(1000))
+        if what == "coarse":   # (a level <= 0, boxes of any size down to 2^3)
+            return ("perm", lo + r(1 - lo), r(1000))
+        return (what, lo + r(hi - lo + 1), r(1000))
+
+    scale, flag = (lambda: rng.choice([1.0, -1.0, 0.37])), (lambda: bool(r(2)))
+    centering = lambda: rng.choice(["cell", "face"])   # noqa: E731
+    if kind in ("put_dense", "get_dense", "get_dense_grad"):
+        lvl, win = lo + r(hi - lo + 1), rng.choice(["whole", "cut"])
+        if kind == "put_dense":
+            return (kind, lvl, 1 + r(2), win)
+        iv = rng.choice([1, 2, 4])
+        return (kind, lvl, iv, win) if kind == "get_dense" else (kind, lvl, iv, win, scale(), flag())
+    if kind == "put_boxes":
+        return (kind, sel(), 1 + r(2), flag())
+    if kind == "put_boxes_div":
+        return (kind, sel(), 1 + r(2), centering(), scale())
+    iv = rng.choice([1, 2, 4])
+    if kind == "get_boxes":
+        return (kind, sel(), iv, flag(), flag())
+    if kind == "get_boxes_grad":
+        return (kind, sel(), iv, centering(), scale(), flag())
+    return (kind, sel(), iv, centering(), scale(), flag(), rng.choice([0, I_COEF]), flag())
+
+
+DEVIO_DECK_SEED = 5
+
+
+def _devio_deal(tree, seed):
+    """_deal over a deck of the device I/O kinds and NEW_KINDS, of its own."""
+    cls = tree_class(parse(WALK_TREES[tree]))
+    deck = DEVIO_KINDS + NEW_KINDS
+    random.Random(DEVIO_DECK_SEED).shuffle(deck)
+    pos = 0
+    for t in sorted(WALK_TREES):
+        if tree_class(parse(WALK_TREES[t])) != cls:
+            continue
+        for s in WALK_SEEDS:
+            n = _n_other(walk_steps(t))
+            if (t, s) == (tree, seed):
+                return [deck[(pos + i) % len(deck)] for i in range(n)]
+            pos += n
+    raise KeyError((tree, seed))
+
+
+def devio_walk(tree, seed, n_steps=None, levels=None):
+    """walk()'s scheme (in every three steps one, at a drawn place, is a
+    cycle) over the device I/O kinds and NEW_KINDS: device I/O between
+    subtract_mean, methods, vcycle_to, correct_children, set_rhs and the rest."""
+    cfg = parse(WALK_TREES[tree])
+    n_steps = walk_steps(tree) if n_steps is None else n_steps
+    lo, hi = levels
+    rng = random.Random(1000 + seed)
+    meth = {"smoother": cfg["smoother"], "op": cfg["op"], "sub": cfg["bc"] == "per"}
+    others = _devio_deal(tree, seed)
+    if len(others) < _n_other(n_steps):
+        raise ValueError("walk longer than its deal")
+    rng.shuffle(others)
+    steps = []
+    for g in range(0, n_steps, 3):
+        size = min(3, n_steps - g)
+        at = rng.randrange(size)
+        for i in range(size):
+            if i == at:
+                c = rng.choices([V0, V1, "vcycle_to"], [3, 2, 2])[0]
+                steps.append(c if c != "vcycle_to" else _draw(rng, c, cfg, lo, hi, meth))
+            else:
+                k = others.pop()
+                steps.append(_draw_devio(rng, k, cfg, lo, hi) if k in DEVIO_KINDS else _draw(rng, k, cfg, lo, hi, meth))
+    return steps
+
+
+def ring_devio_writers_list(hi):
+    """ring_writers_list for the device writers of rhs: each followed by two
+    sweeps of the level it wrote.  The block lists are one z-slab of the
+    level's 2048 boxes (the ring-order copy's flag is the level's, not a
+    box's); the last writer is a get of rhs that fills its ghosts."""
+    sm, slab = ("smooth_boxes", hi, 2), ("slab", hi)
+    return [V0, ("put_dense", hi, 2, "cut"), sm, ("put_boxes", slab, 2, False), sm,
+            ("put_boxes_div", slab, 2, "face", 1.0), sm, ("get_boxes_grad", slab, 2, "cell", 1.0, True), sm]
+
+
+# (the steps of ring_devio_writers_list that no comparison follows: the sweeps' covers them)
+DEVIO_RHS_WRITERS = ("put_dense", "put_boxes", "put_boxes_div", "get_boxes_grad")

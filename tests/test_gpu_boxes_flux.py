@@ -14,7 +14,8 @@ accumulate, as random finite doubles (random sign and mantissa bits, exponents
 within 2^-10 .. 2^10: a NaN's payload after an addition is not IEEE's to
 define); every element outside the defined values must keep its bits.
 
- 1. every level of five trees bitwise against numpy, both kernels;
+ 1. every level of six trees bitwise against numpy, both kernels (one of them
+    not cubic: dr, and so the factor f, differs by direction);
  2. without coefficients the bits are get_blocks_grad's;
  3. mixed coefficients and component masks;
  4. block geometry, accumulating, under the routed, tile and per-cell kernel;
@@ -41,10 +42,11 @@ AH8R = "8 32 32 32 2 v gs ahelm 5 sol sol 2 lb 0"      # three coefficients
 BOX5 = "5 10 10 10 1 v gsrb lpl 0 d0 sol 1 lb 0"       # odd box size (denseutil.odd_box_tree)
 BOX6 = "6 12 12 12 1 v gs lpl 0 d0 sol 1 lb 0"         # its coarsest level has one 3^3 box
 STREAM64 = "16 64 64 64 1 v gsrb lpl 0 per sol 1 lb 0"
+NONCUBE_VL = "8 16 24 8 1 v gs vlpl 0 d0 sol 1 lb 0"   # denseutil.NONCUBE with vlpl: dr differs by direction
 # (tree, the coef argument, the coefficient variables it means, the box sizes of its levels)
 TREES = {"vlpl16": (VL16, None, (5, 5, 5), {16, 8, 4, 2}), "vlpl8-refined": (VL8R, None, (5, 5, 5), {8, 4, 2}),
          "ahelm8-refined": (AH8R, None, (5, 6, 7), {8, 4, 2}), "box5": (BOX5, 5, (5, 5, 5), {5}),
-         "box6": (BOX6, 5, (5, 5, 5), {6, 3})}
+         "box6": (BOX6, 5, (5, 5, 5), {6, 3}), "noncube-vlpl": (NONCUBE_VL, None, (5, 5, 5), {8, 4, 2})}
 SCALES = (1.0, -1.0, 0.37)
 CENTRINGS = ("cell", "face")
 SENT = int(U.SENTINEL)
@@ -213,6 +215,10 @@ def test_every_level_bitwise_against_numpy(monkeypatch, name, variant):
     assert mg.flux_coefficients(coef) == iv_coef
     if "refined" in name:
         assert len(tree.lvls[1].ref_bnds)
+    if name.startswith("noncube"):   # (the three factors f_d differ: a kernel that took one for all would fail)
+        assert parse(args)["domain"] == parse(U.NONCUBE)["domain"]
+        for lvl in be.levels():
+            assert len({float(v) for v in tree.dr[lvl]}) == 3, (lvl, tree.dr[lvl])
     tiled = sum(tree.box_size_lvl[lvl] in (16, 8) for lvl in be.levels())
     filled = _filled_phi(be, rng)
     eps = _upload_coefs(be, rng, iv_coef)
@@ -403,7 +409,8 @@ def test_face_centring_needs_a_ghost_layer_and_accumulate_needs_out(geo):
 
 # -- 5. operator consistency ----------------------------------------------------------------
 @pytest.mark.parametrize("variant", ["tile", "generic"])
-@pytest.mark.parametrize("args,lvl", [(VL16, 1), (AH8R, 1), (AH8R, 2)], ids=["vlpl16", "ahelm8", "ahelm8-refined"])
+@pytest.mark.parametrize("args,lvl", [(VL16, 1), (AH8R, 1), (AH8R, 2), (NONCUBE_VL, 1)],
+                         ids=["vlpl16", "ahelm8", "ahelm8-refined", "noncube-vlpl"])
 def test_face_divergence_of_the_flux_is_the_operator(monkeypatch, args, lvl, variant):
     """Per cell |div F - (op + lambda phi)| <= 32 * 2^-53 * sum_q |T_q| with the
     six terms T_q = c_q (u_q - u_0) / dr^2 in numpy.  The factor is derived, not
@@ -414,6 +421,8 @@ def test_face_divergence_of_the_flux_is_the_operator(monkeypatch, args, lvl, var
     mg, tree = be.mg, be.tree
     nc = tree.box_size_lvl[lvl]
     ids = _ids(be, lvl)
+    if args == NONCUBE_VL:   # (each direction has its own dr)
+        assert len({float(v) for v in tree.dr[lvl]}) == 3, tree.dr[lvl]
     rng = np.random.default_rng(77)
     for l in be.levels():
         mg.set_level(l, IPHI, rng.standard_normal((len(_ids(be, l)),) + (tree.box_size_lvl[l] + 2,) * 3))
